@@ -16,10 +16,17 @@ on both sides, a MAX of the elapsed time and a SUM of the counters; after it one
 of u0/status whose global result rank 0 spot-checks against the C restatement.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --config config4 --global-batch 16384
 
-Prints ONE JSON line on rank 0 (driver contract; roofline + cpu_baseline objects).
+Prints ONE JSON line on rank 0 (driver contract).  A plain run sets up, warms up, times the K steps
+and prints the headline (value, ms_per_step, the kernel time and roofline derived from the same
+steps).  ``--full`` adds everything that takes runs of its own: the spot check against the C
+restatement, the OSQP-settings, pipelined and strong-scaling legs, the CPU baseline and the
+config-1 / config-5 lines.  ``--dump-outputs DIR`` writes what the last timed step computed
+(``dump_outputs``); the inputs are seeded, so two builds can be compared output for output.
 
 The distributed helpers (``shard_bounds``, ``DistContext``, ``timed_steps``, ``reduce_stats``,
 ``gather_rows``, ``spot_check``) are plain functions: tests/test_distributed.py drives the same
@@ -183,6 +190,40 @@ def timed_steps(step: Callable[[int], None], steps: int, warmup: int, ctx: DistC
     sync()
     ctx.barrier()
     return time.perf_counter() - t0
+
+
+CLOCK_RAMP_S = 0.2  # GPU work before the warmup steps of a run without --full (the clock ramp)
+
+
+def clock_ramp(step: Callable[[int], None], sync: Callable[[], None], seconds: float = CLOCK_RAMP_S) -> float:
+    """Untimed steps, 16 between device syncs, until `seconds` have passed; returns the seconds spent."""
+    sync()
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < seconds:
+        for _ in range(16):
+            step(-1)
+        sync()
+    return time.perf_counter() - t0
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(out_dir, arrays: Dict[str, np.ndarray], limit: int = DUMP_LIMIT_BYTES, seed: int = 0) -> dict:
+    """Write per-QP result arrays (first axis = QP) as `out_dir`/<name>.npy in float64.  When they
+    exceed `limit` bytes together, the same seeded sample of rows of every array is written, and the
+    rows' indices beside it (sample_rows.npy).  Returns {name: shape written}."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    rows = len(next(iter(arrays.values())))
+    per_row = 8 + sum(8 * int(np.prod(a.shape[1:], dtype=np.int64)) for a in arrays.values())
+    idx = None
+    if rows * per_row > limit:
+        idx = np.sort(np.random.default_rng(seed).choice(rows, size=max(1, limit // per_row), replace=False))
+        arrays = {**{k: a[idx] for k, a in arrays.items()}, "sample_rows": idx}
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", np.ascontiguousarray(a, dtype=np.float64))
+    return {k: list(a.shape) for k, a in arrays.items()}
 
 
 def reduce_stats(ctx: DistContext, elapsed: float, sums: List[float]) -> Tuple[float, List[float]]:
@@ -900,7 +941,9 @@ def main() -> int:
     # steady state: ~100 untimed steps bring the GPU to its sustained clocks (20 timed after 3 warm
     # steps read ~8 % low: tools/diag/gpu_steps_warmup.sh); the whole default run still takes seconds
     ap.add_argument("--steps", type=int, default=100)
-    ap.add_argument("--warmup", type=int, default=100)
+    ap.add_argument("--warmup", type=int, default=100,
+                    help="untimed steps before the timed ones; a run without --full first runs CLOCK_RAMP_S (0.2 s) "
+                         "of the same step, also untimed, whatever this count is (clock_ramp_ms in the line)")
     ap.add_argument("--config", default="config3", choices=sorted(DEFAULT_BATCH))
     ap.add_argument("--batch", type=int, default=0, help="QPs per GPU, weak scaling (default: the config's)")
     ap.add_argument("--global-batch", type=int, default=0,
@@ -931,7 +974,17 @@ def main() -> int:
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to rehearse "
                          "several ranks on one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the spot check against the C restatement, the "
+                         "OSQP-settings, pipelined and config-4 strong-scaling legs, the CPU baseline and the "
+                         "config-1 / config-5 lines (--cpu-seconds, --check-sample and the --no-* options select "
+                         "among them); off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (u0, X, U, status, iters, active "
+                         "of every QP, all ranks' rows in rank order) as DIR/<name>.npy in float64")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     bad = world_mismatch(args.gpus)
     if bad:
         print(f"bench.py: {bad}", file=sys.stderr)
@@ -998,17 +1051,21 @@ def main() -> int:
     # takes 203 -> 188 us over its first ~80 launches; 20 steps after 5 warm ones read 8 % low,
     # profiles/r06/warmup_matrix.txt), so the headline's K steps run at the clock the GPU holds under
     # load rather than inside its ramp.  The line records the order (leg_order).
+    # Without --full none of those legs runs: the headline's own step, untimed, takes their place for
+    # CLOCK_RAMP_S of GPU work before the W warmup steps, so the K steps are timed at the same
+    # sustained clock and `value` means what it does beside the legs (the line records clock_ramp_ms).
     headline = args.config == "config3" and not args.horizon and not strong
-    strong_batch = make_global_batch("config4", 16384) if headline and not args.no_strong else None
+    strong_batch = make_global_batch("config4", 16384) if args.full and headline and not args.no_strong else None
     pre_legs = {}
-    if world == 1 and not args.no_osqp_settings:
+    if args.full and world == 1 and not args.no_osqp_settings:
         pre_legs["osqp_settings"] = osqp_settings_leg(params, x0, ref, u_prev, args.steps, args.warmup, device,
                                                       args.method, extra, min(args.check_sample, 256))
-    if world == 1 and not args.no_pipelined:
+    if args.full and world == 1 and not args.no_pipelined:
         pre_legs["pipelined"] = pipelined_leg(params, x0, ref, u_prev, args.steps, args.warmup, device,
                                               args.method, extra)
     if strong_batch is not None:  # every rank (collectives in its record step, after the headline)
         pre_legs["strong_config4"] = strong_leg(ctx, args.steps, args.warmup, args.method, extra, batch=strong_batch)
+    ramp_ms = 0.0 if args.full else 1e3 * clock_ramp(step, lambda: torch.cuda.synchronize(device))
     elapsed = timed_steps(step, args.steps, args.warmup, ctx, lambda: torch.cuda.synchronize(device))
     timed = events[::args.event_every]
     if fused:
@@ -1025,11 +1082,14 @@ def main() -> int:
     T, (solved_all, flops_all, admm_all, pol_all) = reduce_stats(
         ctx, elapsed, [float((status == 1).sum()), float(flops.sum()), float(iters[:, 0].sum()),
                        float(iters[:, 1].sum())])
-    # end-of-run gather of the per-QP results (u0, status, U, active) to every rank
-    g = {k: gather_rows(ctx, t[:B], counts) for k, t in
-         (("u0", ctrl._u0), ("status", ctrl._status), ("U", ctrl._U), ("active", ctrl._active),
-          ("iters", ctrl._iters))}
-    g = {k: v.cpu().numpy() for k, v in g.items()}
+    # end-of-run gather of the per-QP results (u0, status, U, active) to every rank, for the checker
+    # leg and --dump-outputs (which writes the predicted states X too)
+    g = {}
+    if args.full or args.dump_outputs:
+        g = {k: gather_rows(ctx, t[:B], counts) for k, t in
+             (("u0", ctrl._u0), ("status", ctrl._status), ("U", ctrl._U), ("active", ctrl._active),
+              ("iters", ctrl._iters)) + ((("X", ctrl._X),) if args.dump_outputs else ())}
+        g = {k: v.cpu().numpy() for k, v in g.items()}
 
     if rank == 0:
         value = solved_all * args.steps / T
@@ -1111,8 +1171,13 @@ def main() -> int:
                 "note": "compulsory f64 I/O per QP over the whole step; not the binding roof",
             },
         }
+        if not args.full:
+            out["clock_ramp_ms"] = ramp_ms  # untimed headline steps before the warmup (clock_ramp)
+        if args.dump_outputs:
+            out["dumped_outputs"] = dump_outputs(args.dump_outputs, {k: g[k] for k in
+                                                                     ("u0", "X", "U", "status", "iters", "active")})
         # checker leg: the gathered global result against the C restatement on a strided sample
-        if args.check_sample > 0:
+        if args.full and args.check_sample > 0:
             idx = np.unique(np.linspace(0, total - 1, min(total, args.check_sample)).astype(int))
             out["rel_err"] = spot_check(params, batch.x0, batch.ref, batch.u_prev, g["U"], g["active"],
                                         g["status"], idx, g["iters"], settings=extra)
@@ -1124,7 +1189,7 @@ def main() -> int:
         rec = pre_legs["strong_config4"]()
         if rank == 0:
             out["strong_config4"] = rec
-    if headline and world > 1 and not args.no_config5:
+    if args.full and headline and world > 1 and not args.no_config5:
         rec = config5_swarm_sharded(ctx)
         if rank == 0:
             out["config5"] = rec
@@ -1134,11 +1199,11 @@ def main() -> int:
         if "osqp_settings" in pre_legs:
             out["osqp_settings"] = pre_legs["osqp_settings"]()
         out["leg_order"] = list(pre_legs) + ["headline"]
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             out["cpu_baseline"] = cpu_baseline(params, x0, ref, u_prev, args.cpu_seconds, settings=extra)
-        if world == 1 and not args.no_config1:
+        if args.full and world == 1 and not args.no_config1:
             out["config1"] = config1_closed_loop()
-        if world == 1 and not args.no_config5 and args.config == "config3" and not args.horizon:
+        if args.full and world == 1 and not args.no_config5 and args.config == "config3" and not args.horizon:
             out["config5"] = config5_swarm()
         if world == 1:
             print(json.dumps(out), flush=True)
@@ -1148,7 +1213,7 @@ def main() -> int:
     if rank == 0 and world > 1:
         # the N-rank line carries the CPU baseline too: rank 0 times it after every rank's GPU legs and
         # collectives are over (the other ranks are leaving, so it does not share their host cores)
-        if args.cpu_seconds > 0:
+        if args.full and args.cpu_seconds > 0:
             out["cpu_baseline"] = cpu_baseline(params, x0, ref, u_prev, args.cpu_seconds, settings=extra)
             out["cpu_baseline"]["note"] = (f"measured on rank 0 after the {world} ranks' timed legs: the host CPU "
                                            f"share of one GPU (threads) and one core, on rank 0's shard")

@@ -16,7 +16,7 @@ import sys
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
-HEAD = ["--cpu-seconds", "0", "--no-config1", "--no-config5", "--no-osqp-settings", "--no-pipelined", "--no-strong"]
+HEAD = ["--full", "--cpu-seconds", "0", "--no-config1", "--no-config5", "--no-osqp-settings", "--no-pipelined", "--no-strong"]
 LEGS = {
     "c3": ["--check-sample", "128"],
     "c2": ["--config", "config2", "--check-sample", "64"],

@@ -10,8 +10,8 @@ timeout -k 10 120 python tools/stamps.py config3 --horizon 10 --batch 256 > $O/a
 for r in 1 2; do
   for L in new base; do
     if [ $L = base ]; then export MPCQP_LIB=$R/tools/diag/libmpcqp_base.so MPCQP_ABI_ANY=1; else unset MPCQP_LIB MPCQP_ABI_ANY; fi
-    timeout -k 10 200 python bench.py --cpu-seconds 0 --no-config1 --no-config5 --check-sample 64 > $O/ab_${L}_c3_$r.json 2> $O/ab_${L}_c3_$r.err || exit 1
-    timeout -k 10 200 python bench.py --config config2 --cpu-seconds 0 --no-config1 --check-sample 64 > $O/ab_${L}_c2_$r.json 2> $O/ab_${L}_c2_$r.err || exit 1
+    timeout -k 10 200 python bench.py --full --cpu-seconds 0 --no-config1 --no-config5 --check-sample 64 > $O/ab_${L}_c3_$r.json 2> $O/ab_${L}_c3_$r.err || exit 1
+    timeout -k 10 200 python bench.py --full --config config2 --cpu-seconds 0 --no-config1 --check-sample 64 > $O/ab_${L}_c2_$r.json 2> $O/ab_${L}_c2_$r.err || exit 1
   done
 done
 unset MPCQP_LIB MPCQP_ABI_ANY

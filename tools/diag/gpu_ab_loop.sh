@@ -8,7 +8,7 @@ rc=$?; tail -3 $O/abl_pytest.log
 for r in 1 2; do
   for L in new base; do
     if [ $L = base ]; then export MPCQP_LIB=$R/tools/diag/libmpcqp_base.so MPCQP_ABI_ANY=1; else unset MPCQP_LIB MPCQP_ABI_ANY; fi
-    timeout -k 10 200 python bench.py --steps 5 --warmup 2 --cpu-seconds 0 --no-config5 --check-sample 64 > $O/abl_${L}_$r.json 2> $O/abl_${L}_$r.err || exit 1
+    timeout -k 10 200 python bench.py --full --steps 5 --warmup 2 --cpu-seconds 0 --no-config5 --check-sample 64 > $O/abl_${L}_$r.json 2> $O/abl_${L}_$r.err || exit 1
     timeout -k 10 200 python -u tools/fleet_bench.py --fused --vehicles 1 100 1024 > $O/abl_${L}_fleet_$r.json 2> $O/abl_${L}_fleet_$r.err || exit 1
   done
 done

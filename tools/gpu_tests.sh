@@ -9,7 +9,7 @@ rc=$?
 tail -5 $O/pytest_gpu.log
 [ $rc -ne 0 ] && [ $rc -ne 1 ] && exit $rc
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 &&
-timeout -k 10 300 python bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 300 python bench.py --full > $O/bench.json 2> $O/bench.err
 brc=$?
 echo "pytest $rc bench $brc"
 exit $(( rc != 0 ? rc : brc ))

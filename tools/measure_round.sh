@@ -2,16 +2,16 @@
 # kernel trace (whole line and headline only), PMC passes on the headline launch, config lines.
 set -o pipefail
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/${TAG:-round}; mkdir -p $O
-HEAD="--cpu-seconds 0 --no-config1 --no-config5 --no-osqp-settings --no-pipelined --no-strong"
+HEAD="--full --cpu-seconds 0 --no-config1 --no-config5 --no-osqp-settings --no-pipelined --no-strong"
 # the sweep microbenchmark when it was built here beforehand (hipcc --offload-arch=gfx950 -O3 -o
 # tools/micro/sweep_bench tools/micro/sweep_bench.hip)
 { [ ! -x tools/micro/sweep_bench ] || timeout -k 10 120 tools/micro/sweep_bench > $O/sweep_bench.json 2> $O/sweep_bench.err; } &&
 timeout -k 10 400 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread > $O/pytest_gpu.log 2>&1 &&
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 &&
-timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err &&
+timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err &&
 timeout -k 10 300 python bench.py $HEAD > $O/bench_steady.json 2>> $O/bench.err &&
 cd /tmp && export TMPDIR=/tmp &&
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run -f csv -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_prof.json 2> $O/bench_prof.err &&
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run -f csv -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_prof.json 2> $O/bench_prof.err &&
 timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $O/prof_head -o run -f csv -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 $HEAD > $O/bench_prof_head.json 2> $O/bench_prof_head.err &&
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_fetch -o run -f csv -- python3 $R/bench.py --steps 3 --warmup 1 $HEAD > $O/pmc_fetch.log 2>&1 &&
 timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE -d $O/pmc_write -o run -f csv -- python3 $R/bench.py --steps 3 --warmup 1 $HEAD > $O/pmc_write.log 2>&1 &&
@@ -28,5 +28,5 @@ timeout -k 10 200 python bench.py --horizon 48 --steps 10 --warmup 5 $HEAD --che
 timeout -k 10 200 python bench.py --horizon 56 --steps 10 --warmup 5 $HEAD --check-sample 32 > $O/N56.json 2>> $O/c.err &&
 timeout -k 10 200 python bench.py --horizon 64 --steps 10 --warmup 5 $HEAD --check-sample 32 > $O/N64.json 2>> $O/c.err &&
 timeout -k 10 200 python -u tools/b1_latency.py > $O/b1_latency.json 2> $O/b1.err &&
-timeout -k 10 300 python bench.py --gpus 2 --backend gloo --steps 20 --warmup 5 > $O/gloo2.json 2> $O/gloo2.err
+timeout -k 10 300 python bench.py --gpus 2 --backend gloo --steps 20 --warmup 5 --full > $O/gloo2.json 2> $O/gloo2.err
 rc=$?; echo "exit $rc"; tail -2 $O/pytest_gpu.log; exit $rc
