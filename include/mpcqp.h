@@ -226,6 +226,37 @@ int mpcqp_solve_served(mpcqp_ws* ws);
 int mpcqp_set_pairing(mpcqp_ws* ws, int mode);
 
 /*
+ * Per-QP parameter classes: one launch for a batch whose QPs do not share one parameter block (a fleet
+ * with two wheelbases or speed limits, a sweep over Q / R / slack weights, nominal and relaxed du_bounds
+ * side by side).  No counterpart in the reference (one MPCParameters per controller, one QP per call).
+ * Additive to ABI 9: no existing struct or call changes.
+ *
+ * Limits: a mixed build never runs two QPs per wave (the halves of a wave would need two blocks):
+ * mpcqp_set_pairing is ignored for it.  The B = 1 paths (mpcqp_solve_staged, mpcqp_solve_served), the
+ * fleet (mpcqp_fleet_*) and the swarm (mpcqp_swarm_*) keep using the workspace's own block, whatever
+ * table it holds.
+ */
+#define MPCQP_BAD_CLASS (-11)   /* per-QP status: class index outside [0, K) */
+
+/* K parameter blocks ("classes") for mixed batches; host array, copied to a device table owned by the
+ * workspace (synchronous; not inside a stream capture -> MPCQP_E_STATE).  K = 0 / blocks = NULL drops
+ * the table.  Every block passes the checks of mpcqp_create and has the workspace's horizon and
+ * reproducible flag; debug_state must be 0 in every block and in the workspace (MPCQP_E_ARG otherwise).
+ * Everything else may differ per class: wheelbase, dt, Q/R/Q_N, all bounds, slack weights, method and
+ * every solver setting.  Invalidates the last build, as mpcqp_set_params does; mpcqp_set_params itself
+ * leaves the table alone. */
+int mpcqp_set_classes(mpcqp_ws* ws, int K, const mpcqp_params* blocks);
+
+/* mpcqp_build for a mixed batch: cls[b] (device, int32) selects QP b's block.  The next mpcqp_solve of
+ * the same B solves every QP under its own block.  cls must stay valid until that solve has run
+ * (stream order), like x0 / ref / u_prev of the fused build.  MPCQP_E_STATE without a class table.
+ * The device checks cls[b] before it indexes the table: a QP whose index lies outside [0, K) gets
+ * status MPCQP_BAD_CLASS and iters {0,0,0,0}, none of its other outputs is written, and the other QPs
+ * of the launch are solved as usual.  A later plain mpcqp_build returns the workspace to its own block. */
+int mpcqp_build_mixed(mpcqp_ws* ws, int B, const double* x0, const double* ref, const double* u_prev,
+                      const int32_t* cls, void* stream);
+
+/*
  * Closed-loop fleet: V vehicles tracking their own references, one MPC step each per call
  * (SURVEY.md §8f row 1).  Replaces, per vehicle, one iteration of the loop body of
  * TrajectoryTracker.track (src/pipeline/control_stage.py:100-150):

@@ -28,13 +28,10 @@ using mpcqp::Launch;
 // ------------------------------------------------------------------ K1: build
 // Per QP (one wave, lane k = horizon step k in [0, N]) on caller-provided windows; the body
 // (unwrap + linearize) is build_qp in mpcqp_build.h.
-__global__ __launch_bounds__(kWave) void k_build(mpcqp_params p, int B, const double* __restrict__ x0,
-                                                 const double* __restrict__ ref,
-                                                 const double* __restrict__ u_prev,
-                                                 double* __restrict__ model) {
-  const int b = blockIdx.x;
+__device__ __forceinline__ void build_window(const mpcqp_params& p, int b, const double* __restrict__ x0,
+                                             const double* __restrict__ ref, const double* __restrict__ u_prev,
+                                             double* __restrict__ model) {
   const int lane = threadIdx.x;
-  if (b >= B) return;
   const int N = p.horizon;
   const double* rb = ref + (size_t)b * (N + 1) * 4;
   const double x0l = lane < 4 ? x0[(size_t)b * 4 + lane] : 0.0;
@@ -59,6 +56,31 @@ __global__ __launch_bounds__(kWave) void k_build(mpcqp_params p, int B, const do
     rv = rb[4 * lane + 3];
   }
   build_qp(p, lane, rx, ry, ryaw, rv, x0l, upl, model + (size_t)b * model_stride(N));
+}
+
+__global__ __launch_bounds__(kWave) void k_build(mpcqp_params p, int B, const double* __restrict__ x0,
+                                                 const double* __restrict__ ref,
+                                                 const double* __restrict__ u_prev,
+                                                 double* __restrict__ model) {
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  build_window(p, b, x0, ref, u_prev, model);
+}
+
+// K1 of a mixed batch (mpcqp_build_mixed, the workgroup-per-QP families): QP b's model under its own
+// block P[cls[b]] (dt, wheelbase).  A class index outside [0, K) writes no model; the solve kernel
+// reports that QP as MPCQP_BAD_CLASS and does not read it.
+__global__ __launch_bounds__(kWave) void k_build_mixed(const mpcqp_params* __restrict__ P,
+                                                       const int32_t* __restrict__ cls, int K, int B,
+                                                       const double* __restrict__ x0,
+                                                       const double* __restrict__ ref,
+                                                       const double* __restrict__ u_prev,
+                                                       double* __restrict__ model) {
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  const int c = cls[b];
+  if ((unsigned)c >= (unsigned)K) return;
+  build_window(P[c], b, x0, ref, u_prev, model);
 }
 
 // ------------------------------------------------------------------ test hook: wave primitives
@@ -91,6 +113,19 @@ const mpcqp::launcher_t kLaunchers[MPCQP_WIDE_MIN_HORIZON] = {
     MPCQP_L(24), MPCQP_L(25), MPCQP_L(26), MPCQP_L(27), MPCQP_L(28), MPCQP_L(29), MPCQP_L(30), MPCQP_L(31),
     MPCQP_L(32)};
 #undef MPCQP_L
+#ifdef MPCQP_ONLY_N
+#define MPCQP_M(N) ((N) == MPCQP_ONLY_N ? &mpcqp::launch_solve_mixed<MPCQP_ONLY_N> : nullptr)
+#else
+#define MPCQP_M(N) &mpcqp::launch_solve_mixed<N>
+#endif
+// k_solve_mixed<N>: the one-wave kernel with a parameter block per QP (mpcqp_build_mixed)
+const mpcqp::launcher_t kMixedLaunchers[MPCQP_WIDE_MIN_HORIZON] = {
+    nullptr,     MPCQP_M(1),  MPCQP_M(2),  MPCQP_M(3),  MPCQP_M(4),  MPCQP_M(5),  MPCQP_M(6),  MPCQP_M(7),
+    MPCQP_M(8),  MPCQP_M(9),  MPCQP_M(10), MPCQP_M(11), MPCQP_M(12), MPCQP_M(13), MPCQP_M(14), MPCQP_M(15),
+    MPCQP_M(16), MPCQP_M(17), MPCQP_M(18), MPCQP_M(19), MPCQP_M(20), MPCQP_M(21), MPCQP_M(22), MPCQP_M(23),
+    MPCQP_M(24), MPCQP_M(25), MPCQP_M(26), MPCQP_M(27), MPCQP_M(28), MPCQP_M(29), MPCQP_M(30), MPCQP_M(31),
+    MPCQP_M(32)};
+#undef MPCQP_M
 #ifdef MPCQP_ONLY_N
 #define MPCQP_F(N) ((N) == MPCQP_ONLY_N ? &mpcqp::launch_fleet_loop<MPCQP_ONLY_N> : nullptr)
 #else
@@ -136,6 +171,15 @@ size_t ws_state_stride(int N, bool wide) {
 }
 
 void launch_mid(hipStream_t s, const Launch& L) {
+  if (L.cls) {  // a parameter block per QP (mpcqp_build_mixed)
+    switch (mpcqp::mid_bucket(L.p->horizon)) {
+      case 40: mpcqp::launch_solve_mid_mixed<40>(s, L); break;
+      case 48: mpcqp::launch_solve_mid_mixed<48>(s, L); break;
+      case 56: mpcqp::launch_solve_mid_mixed<56>(s, L); break;
+      default: mpcqp::launch_solve_mid_mixed<64>(s, L); break;
+    }
+    return;
+  }
   switch (mpcqp::mid_bucket(L.p->horizon)) {  // N >= 33: N = 32 runs the one-wave kernel
     case 40: mpcqp::launch_solve_mid<40>(s, L); break;
     case 48: mpcqp::launch_solve_mid<48>(s, L); break;
@@ -205,6 +249,9 @@ serve_t server(const mpcqp_params& p) {
 }
 bool use_pairs(const mpcqp_ws* ws, int count) {
   const mpcqp_params& p = ws->p;
+  // a mixed build (mpcqp_build_mixed) never pairs: the two halves of a wave would need two parameter
+  // blocks, which turns every parameter into a per-lane value
+  if (ws->in_cls) return false;
   if (wide_solve(p) || p.debug_state || p.horizon < 1 || p.horizon > kPairMaxHorizon || !kPairLaunchers[p.horizon])
     return false;
   if (ws->pairing == MPCQP_PAIR_ON) return true;
@@ -257,6 +304,9 @@ int mpcqp_create(const mpcqp_params* p, int max_batch, int device, mpcqp_ws** ws
   w->serve_broken = false;
   w->serve_fault = 0;
   w->pairing = MPCQP_PAIR_AUTO;
+  w->dclasses = nullptr;
+  w->n_classes = 0;
+  w->in_cls = nullptr;
   if (hipDeviceGetAttribute(&w->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) w->cus = 0;
   e = hipMalloc(&w->dparams, 2 * sizeof(mpcqp_params));
   if (e == hipSuccess) e = hipMalloc(&w->dorder, sizeof(int32_t) * (size_t)max_batch);
@@ -290,6 +340,55 @@ int mpcqp_set_params(mpcqp_ws* ws, const mpcqp_params* p) {
   // invalidate it, and the next mpcqp_solve needs a new mpcqp_build.
   ws->built_B = -1;
   ws->in_x0 = ws->in_ref = ws->in_up = nullptr;
+  ws->in_cls = nullptr;
+  return MPCQP_OK;
+}
+
+int mpcqp_set_classes(mpcqp_ws* ws, int K, const mpcqp_params* blocks) {
+  if (!ws) return fail(MPCQP_E_ARG, "null ws");
+  if (K < 0 || (K > 0 && !blocks)) return fail(MPCQP_E_ARG, "set_classes needs K >= 0 and K blocks");
+  if (!blocks) K = 0;
+  for (int k = 0; k < K; ++k) {
+    const int rc = check_params(&blocks[k]);
+    if (rc) return rc;
+    if (blocks[k].horizon != ws->p.horizon)
+      return fail(MPCQP_E_HORIZON, "class " + std::to_string(k) + " has another horizon than the workspace");
+    if (blocks[k].reproducible != ws->p.reproducible)
+      return fail(MPCQP_E_ARG, "class " + std::to_string(k) + " has another reproducible flag than the workspace");
+    if (blocks[k].debug_state) return fail(MPCQP_E_ARG, "class " + std::to_string(k) + " sets debug_state");
+  }
+  if (K > 0 && ws->p.debug_state) return fail(MPCQP_E_ARG, "classes need a workspace without debug_state");
+  // the table is allocated and copied synchronously, which a stream capture cannot record (the legacy
+  // stream reports a capture in progress on a blocking stream without invalidating it)
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(nullptr, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
+    (void)hipGetLastError();
+    return fail(MPCQP_E_STATE, "mpcqp_set_classes inside a stream capture");
+  }
+  int cur = -1;
+  hipError_t e = hipGetDevice(&cur);
+  if (e == hipSuccess && cur != ws->device) e = hipSetDevice(ws->device);
+  mpcqp_params* table = nullptr;
+  if (e == hipSuccess && K > 0) e = hipMalloc(&table, sizeof(mpcqp_params) * (size_t)K);
+  if (e == hipSuccess && K > 0) e = hipMemcpy(table, blocks, sizeof(mpcqp_params) * (size_t)K, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    // a build belongs to the table it was made with; hipFree waits for the launches that read the old one
+    if (ws->dclasses) {
+      serve_stop(ws);  // (a resident B = 1 wave would keep that wait until it goes idle)
+      (void)hipFree(ws->dclasses);
+    }
+    ws->dclasses = table;
+    ws->n_classes = K;
+    ws->built_B = -1;
+    ws->in_x0 = ws->in_ref = ws->in_up = nullptr;
+    ws->in_cls = nullptr;
+  } else if (table) {
+    (void)hipFree(table);
+  }
+  if (cur >= 0 && cur != ws->device) (void)hipSetDevice(cur);
+  if (e == hipErrorStreamCaptureUnsupported || e == hipErrorStreamCaptureImplicit)
+    return fail(MPCQP_E_STATE, "mpcqp_set_classes inside a stream capture");
+  if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("class table: ") + hipGetErrorString(e));
   return MPCQP_OK;
 }
 
@@ -302,6 +401,7 @@ void mpcqp_destroy(mpcqp_ws* ws) {
   (void)hipFree(ws->state);
   (void)hipFree(ws->dparams);
   (void)hipFree(ws->dorder);
+  (void)hipFree(ws->dclasses);
   if (ws->serve_box) (void)hipHostFree(ws->serve_box);
   if (ws->stage_in) (void)hipHostFree(ws->stage_in);
   if (ws->stage_out) (void)hipHostFree(ws->stage_out);
@@ -322,6 +422,7 @@ int mpcqp_build(mpcqp_ws* ws, int B, const double* x0, const double* ref, const 
   if (B < 0 || B > ws->max_batch) return fail(MPCQP_E_BATCH, "batch exceeds workspace capacity");
   ws->built_B = B;
   ws->in_x0 = ws->in_ref = ws->in_up = nullptr;
+  ws->in_cls = nullptr;
   if (B == 0) return MPCQP_OK;
   // The one-wave solve builds the model itself (K1 fused into k_solve: the model block never
   // touches HBM); the K1 kernel runs only for the long-horizon solve and for inspection builds.
@@ -343,6 +444,35 @@ int mpcqp_build(mpcqp_ws* ws, int B, const double* x0, const double* ref, const 
   return MPCQP_OK;
 }
 
+int mpcqp_build_mixed(mpcqp_ws* ws, int B, const double* x0, const double* ref, const double* u_prev,
+                      const int32_t* cls, void* stream) {
+  if (!ws || !x0 || !ref || !cls) return fail(MPCQP_E_ARG, "null argument");
+  if (!ws->dclasses) return fail(MPCQP_E_STATE, "mpcqp_build_mixed without a class table (mpcqp_set_classes)");
+  if (B < 0 || B > ws->max_batch) return fail(MPCQP_E_BATCH, "batch exceeds workspace capacity");
+  if (ws->p.debug_state) return fail(MPCQP_E_ARG, "mpcqp_build_mixed needs a workspace without debug_state");
+  ws->built_B = -1;
+  ws->in_x0 = ws->in_ref = ws->in_up = nullptr;
+  ws->in_cls = nullptr;
+  if (B > 0) {
+    if (!mpcqp::wide_solve(ws->p)) {  // the one-wave solve builds each model itself, under the QP's block
+      ws->in_x0 = x0;
+      ws->in_ref = ref;
+      ws->in_up = u_prev;
+    } else {
+      hipStream_t s = static_cast<hipStream_t>(stream);
+      const int rc = mpcqp::ensure_buffers(ws, true, true, s);
+      if (rc) return rc;
+      hipLaunchKernelGGL(k_build_mixed, dim3(B), dim3(kWave), 0, s, ws->dclasses, cls, ws->n_classes, B, x0, ref,
+                         u_prev, ws->model);
+      hipError_t e = hipGetLastError();
+      if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("k_build_mixed launch: ") + hipGetErrorString(e));
+    }
+  }
+  ws->in_cls = cls;
+  ws->built_B = B;
+  return MPCQP_OK;
+}
+
 int mpcqp_solve(mpcqp_ws* ws, int B, double* u0, double* X, double* U, int32_t* status, int32_t* iters,
                 uint8_t* active, void* stream) {
   if (!ws || !status) return fail(MPCQP_E_ARG, "null argument");
@@ -353,6 +483,16 @@ int mpcqp_solve(mpcqp_ws* ws, int B, double* u0, double* X, double* U, int32_t* 
   L.x0 = ws->in_x0;
   L.ref = ws->in_ref;
   L.u_prev = ws->in_up;
+  if (ws->in_cls) {  // the last build was mpcqp_build_mixed: a parameter block per QP, never paired
+    L.table = ws->dclasses;
+    L.cls = ws->in_cls;
+    L.K = ws->n_classes;
+    // the workgroup-per-QP launchers read L.cls themselves; the one-wave kernel has its own table
+    (mpcqp::wide_solve(ws->p) ? mpcqp::launcher(ws->p) : kMixedLaunchers[ws->p.horizon])(s, L);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("k_solve_mixed launch: ") + hipGetErrorString(e));
+    return MPCQP_OK;
+  }
   if (!(L.ref && mpcqp::use_pairs(ws, B) && kPairLaunchers[ws->p.horizon](s, L))) mpcqp::launcher(ws->p)(s, L);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("k_solve launch: ") + hipGetErrorString(e));

@@ -407,6 +407,21 @@ __device__ __forceinline__ double np_mod(double a, double b) {
   return m;
 }
 
+// Per-QP parameter classes (mpcqp_build_mixed): QP b's block is P[cls[b]] of a K-entry table.  The
+// index is checked before it indexes anything: false for (unsigned)c >= K, and thread 0 has then
+// written status[b] = MPCQP_BAD_CLASS and zero iters (nothing else of the QP is written).  The caller
+// returns at once, before any barrier; c is uniform over the QP's wave / workgroup.
+__device__ __forceinline__ bool class_ok(int c, int K, int b, int32_t* __restrict__ statuso,
+                                         int32_t* __restrict__ iterso) {
+  if ((unsigned)c < (unsigned)K) return true;
+  if (threadIdx.x == 0) {
+    statuso[b] = MPCQP_BAD_CLASS;
+    if (iterso)
+      for (int i = 0; i < 4; ++i) iterso[4 * (size_t)b + i] = 0;
+  }
+  return false;
+}
+
 }  // namespace
 
 namespace mpcqp {
@@ -425,6 +440,11 @@ struct Launch {
   const double* x0 = nullptr;
   const double* ref = nullptr;
   const double* u_prev = nullptr;
+  // per-QP parameter classes (mpcqp_build_mixed): with cls != nullptr QP b runs under table[cls[b]]
+  // (K blocks in device memory, the workspace's horizon and kernel family) and p only selects the kernel
+  const mpcqp_params* table = nullptr;
+  const int32_t* cls = nullptr;
+  int K = 0;
 };
 
 typedef void (*launcher_t)(hipStream_t, const Launch&);
@@ -436,6 +456,9 @@ bool launch_solve_pair(hipStream_t s, const Launch& L);
 // mpcqp_part.hip objects (parallel build) or in mpcqp.hip itself (MPCQP_ONLY_N dev builds).
 template <int N>
 void launch_solve(hipStream_t s, const Launch& L);
+// the one-wave kernel with a parameter block per QP (k_solve_mixed<N>: L.table / L.cls / L.K, fused K1)
+template <int N>
+void launch_solve_mixed(hipStream_t s, const Launch& L);
 // the fused closed loop of a fleet (k_fleet_loop<N>, mpcqp_solve.h; N <= 32, fast mode): `steps`
 // loop steps of every RUNNING vehicle in one launch
 // The config-5 replan trigger inside the fused loop (mpcqp_swarm_loop): after each step a RUNNING
@@ -484,12 +507,17 @@ bool use_pairs(const mpcqp_ws* ws, int count);
 // the long-horizon solve (N >= MPCQP_WIDE_MIN_HORIZON; mpcqp_wide.hip): one 256-thread workgroup
 // per QP, L.state = its workspace (wide_stride(N) doubles per QP)
 void launch_solve_wide(hipStream_t s, const Launch& L);
+// the same with a parameter block per QP (k_solve_wide_mixed; an object of its own)
+void launch_solve_wide_mixed(hipStream_t s, const Launch& L);
 size_t wide_stride(int horizon);
 // the mid-horizon fast solve (MPCQP_WIDE_MIN_HORIZON <= N <= MPCQP_MID_MAX_HORIZON, mpcqp_mid.hip):
 // one workgroup of 4 x (1 or 2) waves per QP, instantiated per padded horizon bucket NT; L.state = its
 // workspace (mid_stride(N) doubles per QP: the scaled Hessian)
 template <int NT>
 void launch_solve_mid(hipStream_t s, const Launch& L);
+// the same with a parameter block per QP (k_solve_mid_mixed<NT>; an object of its own per bucket)
+template <int NT>
+void launch_solve_mid_mixed(hipStream_t s, const Launch& L);
 inline int mid_bucket(int N) { return N <= 40 ? 40 : (N <= 48 ? 48 : (N <= 56 ? 56 : 64)); }  // N >= 33
 inline size_t mid_stride(int N) { return (size_t)2 * mid_bucket(N) * 128; }
 // the solve of this parameter block runs a workgroup-per-QP kernel (long horizon or reproducible)
@@ -542,6 +570,11 @@ struct mpcqp_ws {
   // two QPs per wave for N <= 15 (MPCQP_PAIR_*, mpcqp_set_pairing)
   int pairing;
   int cus;  // the device's compute units (queried once at mpcqp_create; 0 if unknown)
+  // per-QP parameter classes (mpcqp_set_classes): the device table of n_classes blocks, and the class
+  // indices of the last build when that was an mpcqp_build_mixed (nullptr after a plain mpcqp_build)
+  mpcqp_params* dclasses;
+  int n_classes;
+  const int32_t* in_cls;
 };
 
 namespace mpcqp {

@@ -1450,6 +1450,26 @@ __device__ __forceinline__ void mid_finish(const mpcqp_params& p, int b, Mid<NT>
 }
 
 // ------------------------------------------------------------------ the kernel
+// One body, two entry points, each in objects of its own (-DMPCQP_MID_MIXED): k_solve_mid takes the
+// parameter block as a kernel argument; k_solve_mid_mixed (mpcqp_build_mixed) runs QP b's workgroup
+// under P[cls[b]], K blocks in device memory with this horizon, on the model k_build_mixed made under
+// the same block.  An index outside [0, K) is reported per QP and leaves before it indexes the table
+// or reaches a barrier.
+#ifdef MPCQP_MID_MIXED
+template <int NT>
+__global__ __launch_bounds__(MidShape<NT>::kThreads, kMidWaves) void k_solve_mid_mixed(
+    const mpcqp_params* __restrict__ P, const int32_t* __restrict__ cls, int K, int B,
+    const double* __restrict__ model, double* __restrict__ work, double* __restrict__ u0o, double* __restrict__ Xo,
+    double* __restrict__ Uo, int32_t* __restrict__ statuso, int32_t* __restrict__ iterso,
+    uint8_t* __restrict__ activeo) {
+  using S = MidShape<NT>;
+  __shared__ MidLds<NT> sm;
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  const int c = cls[b];
+  if (!class_ok(c, K, b, statuso, iterso)) return;
+  const mpcqp_params& p = P[c];
+#else
 template <int NT>
 __global__ __launch_bounds__(MidShape<NT>::kThreads, kMidWaves) void k_solve_mid(
     mpcqp_params p, int B, const uint8_t* __restrict__ mask, const double* __restrict__ model,
@@ -1459,6 +1479,7 @@ __global__ __launch_bounds__(MidShape<NT>::kThreads, kMidWaves) void k_solve_mid
   __shared__ MidLds<NT> sm;
   const int b = blockIdx.x;
   if (b >= B || (mask && !mask[b])) return;
+#endif
   const int tid = threadIdx.x;
   Mid<NT> C;
   C.sm = &sm;
@@ -1566,19 +1587,30 @@ __global__ __launch_bounds__(MidShape<NT>::kThreads, kMidWaves) void k_solve_mid
 }  // namespace
 
 namespace mpcqp {
+// one bucket per object (parallel build): -DMPCQP_MID_PART=NT; with -DMPCQP_MID_MIXED the object holds
+// the bucket's k_solve_mid_mixed alone, so k_solve_mid is compiled exactly as without the mixed kernel
+// (helpers that two kernels of one object share are inlined differently)
+#ifndef MPCQP_MID_PART
+#error "define MPCQP_MID_PART (the bucket NT of this object)"
+#endif
+#ifdef MPCQP_MID_MIXED
+template <int NT>
+void launch_solve_mid_mixed(hipStream_t s, const Launch& L) {
+  hipLaunchKernelGGL(k_solve_mid_mixed<NT>, dim3(L.B), dim3(MidShape<NT>::kThreads), 0, s, L.table, L.cls, L.K, L.B,
+                     L.model, L.state, L.u0, L.X, L.U, L.st, L.it, L.ac);
+}
+template void launch_solve_mid_mixed<MPCQP_MID_PART>(hipStream_t, const Launch&);
+#else
 template <int NT>
 void launch_solve_mid(hipStream_t s, const Launch& L) {
   hipLaunchKernelGGL(k_solve_mid<NT>, dim3(L.B), dim3(MidShape<NT>::kThreads), 0, s, *L.p, L.B, L.mask, L.model,
                      L.state, L.u0, L.X, L.U, L.st, L.it, L.ac);
 }
-// one bucket per object (parallel build): -DMPCQP_MID_PART=NT
-#ifndef MPCQP_MID_PART
-#error "define MPCQP_MID_PART (the bucket NT of this object)"
-#endif
 template void launch_solve_mid<MPCQP_MID_PART>(hipStream_t, const Launch&);
+#endif
 }  // namespace mpcqp
 
-#ifdef MPCQP_MID_STAMPS
+#if defined(MPCQP_MID_STAMPS) && !defined(MPCQP_MID_MIXED)  // the stamps are the plain kernel's
 #define MPCQP_CAT2(a, b) a##b
 #define MPCQP_CAT(a, b) MPCQP_CAT2(a, b)
 extern "C" int MPCQP_CAT(mpcqp_debug_mid_stamps_, MPCQP_MID_PART)(unsigned long long* out, int reset) {

@@ -536,6 +536,14 @@ struct ServeWin {
   __device__ __forceinline__ int lane() const { return ln; }
 };
 
+// ClassWin: a mixed batch (k_solve_mixed): the caller's buffers exactly as BatchWin.  A type of its own
+// so that setup_qp / finish_qp are instantiated apart from k_solve's: helpers that two kernels share
+// are inlined differently, and the headline kernel's code generation stays what it was.
+struct ClassWin {
+  static constexpr bool kFleet = false;
+  __device__ __forceinline__ int lane() const { return threadIdx.x; }
+};
+
 // ------------------------------------------------------------------ K2 phase 1: setup
 // Condensing (states and slacks eliminated) + OSQP Ruiz/cost scaling.  Leaves the scaled
 // problem on chip for the later phases: Pbar (symmetric, row-major) in the solve LDS, the
@@ -1938,6 +1946,38 @@ __global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_solve_pair(mpcqp
                                iterso, activeo, U);
 }
 
+// ------------------------------------------------------------------ K2, a parameter block per QP
+// Mixed batches (mpcqp_build_mixed): QP b runs under P[cls[b]], one of K blocks in device memory that
+// share the horizon -- wheelbase, dt, weights, bounds, method and solver settings may all differ.
+// The block index is uniform over the wave, so the block arrives through scalar loads as the kernel
+// argument of k_solve does (one copy per QP, see below); the QP goes through solve_one's driver (fused K1 under its own dt and
+// wheelbase), the operations of k_solve on the same values: the results are k_solve's under block
+// cls[b], bit for bit.  An index outside [0, K) is reported per QP and never indexes the table.
+template <int N>
+__global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_solve_mixed(const mpcqp_params* __restrict__ P,
+                                                       const int32_t* __restrict__ cls, int K, int B,
+                                                       const double* __restrict__ in_x0,
+                                                       const double* __restrict__ in_ref,
+                                                       const double* __restrict__ in_up,
+                                                       double* __restrict__ u0o, double* __restrict__ Xo,
+                                                       double* __restrict__ Uo, int32_t* __restrict__ statuso,
+                                                       int32_t* __restrict__ iterso, uint8_t* __restrict__ activeo) {
+  __shared__ SolveLds<N> sm;
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  const int c = cls[b];
+  if (!class_ok(c, K, b, statuso, iterso)) return;
+  // a copy of the block, not a reference into the table: the compiler does not know loads from global
+  // memory as invariant and would re-read the solver settings in every ADMM iteration (17 scalar loads
+  // inside the iteration loops at N = 20, against one in k_solve, whose kernel-argument block it does
+  // hoist: +10 % per step at B = 4096).  The copy's dynamically indexed arrays (Q, the bounds) live in
+  // scratch, read in setup and outputs only.
+  const mpcqp_params p = P[c];
+  double U;
+  solve_one<N, ClassWin>(p, b, nullptr, in_x0, in_ref, in_up, ClassWin{}, sm, u0o, Xo, Uo, statuso, iterso, activeo,
+                         U);
+}
+
 // ------------------------------------------------------------------ fused closed loop
 // Every vehicle of a fleet runs `steps` iterations of the loop body of TrajectoryTracker.track
 // (control_stage.py:100-150) on its own wave, with no kernel boundary between steps: the window
@@ -2127,6 +2167,11 @@ void launch_solve(hipStream_t s, const Launch& L) {
   hipLaunchKernelGGL(k_solve<N>, dim3(L.B), dim3(kWave), 0, s, *L.p, L.B, L.mask, L.model, L.x0, L.ref, L.u_prev,
                      L.state, L.u0, L.X, L.U,
                      L.st, L.it, L.ac);
+}
+template <int N>
+void launch_solve_mixed(hipStream_t s, const Launch& L) {
+  hipLaunchKernelGGL(k_solve_mixed<N>, dim3(L.B), dim3(kWave), 0, s, L.table, L.cls, L.K, L.B, L.x0, L.ref, L.u_prev,
+                     L.u0, L.X, L.U, L.st, L.it, L.ac);
 }
 template <int N>
 void launch_fleet_loop(hipStream_t s, const mpcqp_params* P, const mpcqp_fleet& f, int steps, const LoopTrigger& tr) {

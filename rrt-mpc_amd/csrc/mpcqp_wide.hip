@@ -1131,6 +1131,26 @@ __device__ void wide_solve(const mpcqp_params& p, Wide& S, bool bad, int b, doub
 // workspace, 0 both in the workspace.  A compile-time choice, so every access is a ds_* or a
 // global_* instruction (a pointer that may be either compiles to flat accesses, which wait for
 // all outstanding memory operations: ~100x slower here).
+// One body, two entry points, each in an object of its own (-DMPCQP_WIDE_MIXED): k_solve_wide takes the
+// parameter block as a kernel argument; k_solve_wide_mixed (mpcqp_build_mixed) runs QP b's workgroup
+// under P[cls[b]], K blocks in device memory with this horizon and reproducible flag (they fix the
+// layout and kMode / FAST), on the model k_build_mixed made under the same block.  An index outside
+// [0, K) is reported per QP and leaves before it indexes the table or reaches a barrier.
+#ifdef MPCQP_WIDE_MIXED
+template <int kMode, bool FAST>
+__global__ __launch_bounds__(kT) void k_solve_wide_mixed(const mpcqp_params* __restrict__ P,
+                                                         const int32_t* __restrict__ cls, int K, int B,
+                                                         const double* __restrict__ model, double* __restrict__ wide,
+                                                         double* __restrict__ u0o, double* __restrict__ Xo,
+                                                         double* __restrict__ Uo, int32_t* __restrict__ statuso,
+                                                         int32_t* __restrict__ iterso, uint8_t* __restrict__ activeo) {
+  extern __shared__ double lds[];
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  const int c = cls[b];
+  if (!class_ok(c, K, b, statuso, iterso)) return;
+  const mpcqp_params& p = P[c];
+#else
 template <int kMode, bool FAST>
 __global__ __launch_bounds__(kT) void k_solve_wide(mpcqp_params p, int B, const uint8_t* __restrict__ mask,
                                                    const double* __restrict__ model, double* __restrict__ wide,
@@ -1140,6 +1160,7 @@ __global__ __launch_bounds__(kT) void k_solve_wide(mpcqp_params p, int B, const 
   extern __shared__ double lds[];
   const int b = blockIdx.x;
   if (b >= B || (mask && !mask[b])) return;
+#endif
   const int N = p.horizon, n = 2 * N;
   Wide S;
   S.L = WideLayout::make(N);
@@ -1178,9 +1199,18 @@ __global__ __launch_bounds__(kT) void k_solve_wide(mpcqp_params p, int B, const 
 }  // namespace
 
 namespace mpcqp {
+// -DMPCQP_WIDE_MIXED: an object of its own with the k_solve_wide_mixed kernels alone, so k_solve_wide is
+// compiled exactly as without them (helpers that two kernels of one object share are inlined differently)
+#ifndef MPCQP_WIDE_MIXED
 size_t wide_stride(int horizon) { return wide_stride_of(WideLayout::make(horizon)); }
+#endif
 
+#ifdef MPCQP_WIDE_MIXED
+void launch_solve_wide_mixed(hipStream_t s, const Launch& L) {
+#else
 void launch_solve_wide(hipStream_t s, const Launch& L) {
+  if (L.cls) return launch_solve_wide_mixed(s, L);  // a parameter block per QP (mpcqp_build_mixed)
+#endif
   double* wide = L.state;
   const WideLayout lay = WideLayout::make(L.p->horizon);
   const size_t arena = sizeof(double) * (size_t)lay.total, pbar = sizeof(double) * (size_t)lay.n * lay.ps;
@@ -1189,16 +1219,28 @@ void launch_solve_wide(hipStream_t s, const Launch& L) {
     if (lds > 65536)
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)lds);
+#ifdef MPCQP_WIDE_MIXED
+    hipLaunchKernelGGL(kern, dim3(L.B), dim3(kT), lds, s, L.table, L.cls, L.K, L.B, L.model, wide, L.u0, L.X, L.U,
+                       L.st, L.it, L.ac);
+#else
     hipLaunchKernelGGL(kern, dim3(L.B), dim3(kT), lds, s, *L.p, L.B, L.mask, L.model, wide, L.u0, L.X, L.U, L.st,
                        L.it, L.ac);
+#endif
   };
   // reproducible = 1: the C restatement op for op; 0 (N >= MPCQP_WIDE_MIN_HORIZON): the fast polish
+  // (every block of a mixed batch has the workspace's horizon and flag: the same choice of kMode / FAST)
   const bool fast = L.p->reproducible == 0;
+#ifdef MPCQP_WIDE_MIXED
+#define MPCQP_WIDE_KERNEL k_solve_wide_mixed
+#else
+#define MPCQP_WIDE_KERNEL k_solve_wide
+#endif
   if (arena + pbar <= kLds)
-    fast ? go(&k_solve_wide<2, true>, arena + pbar) : go(&k_solve_wide<2, false>, arena + pbar);
+    fast ? go(&MPCQP_WIDE_KERNEL<2, true>, arena + pbar) : go(&MPCQP_WIDE_KERNEL<2, false>, arena + pbar);
   else if (arena <= kLds)
-    fast ? go(&k_solve_wide<1, true>, arena) : go(&k_solve_wide<1, false>, arena);
+    fast ? go(&MPCQP_WIDE_KERNEL<1, true>, arena) : go(&MPCQP_WIDE_KERNEL<1, false>, arena);
   else
-    fast ? go(&k_solve_wide<0, true>, 0) : go(&k_solve_wide<0, false>, 0);
+    fast ? go(&MPCQP_WIDE_KERNEL<0, true>, 0) : go(&MPCQP_WIDE_KERNEL<0, false>, 0);
+#undef MPCQP_WIDE_KERNEL
 }
 }  // namespace mpcqp

@@ -23,6 +23,7 @@ SOLVED = 1
 SOLVED_INACCURATE = 2
 MAX_ITER_REACHED = -2
 NUMERICAL_ERROR = -10
+BAD_CLASS = -11  # MPCQP_BAD_CLASS: a mixed batch's class index outside [0, K)
 METHOD_ADMM = 0
 METHOD_NEWTON = 1
 STATUS_NAMES = {
@@ -30,6 +31,7 @@ STATUS_NAMES = {
     SOLVED_INACCURATE: "solved_inaccurate",
     MAX_ITER_REACHED: "maximum_iterations_reached",
     NUMERICAL_ERROR: "numerical_error",
+    BAD_CLASS: "bad_class",
 }
 
 # OSQP settings used by the reference (src/control/mpc_controller.py:121-131) plus the
@@ -124,6 +126,43 @@ def to_c_params(params, method: int = METHOD_ADMM, **settings) -> MpcqpParams:
     for key, value in merged.items():
         setattr(c, key, value)
     return c
+
+
+def class_table(params_list, method="admm", settings=None):
+    """The host array of ``mpcqp_set_classes``: one ``mpcqp_params`` block per entry of
+    ``params_list`` (``MPCParameters``-like objects of one horizon), each filled exactly as
+    ``to_c_params`` fills a workspace's block.  ``method``: "admm" / "newton" (or METHOD_*) for every
+    class, or a list with one per class.  ``settings``: one dict of solver settings for all classes, or
+    a list with one dict per class.  Pure host code; raises ``ValueError`` on an empty list, mixed
+    horizons or ``reproducible`` flags, ``debug_state``, and a list of the wrong length."""
+    params_list = list(params_list)
+    K = len(params_list)
+    if K == 0:
+        raise ValueError("class_table needs at least one parameter block")
+
+    def per_class(value, name):
+        if isinstance(value, (list, tuple)):
+            if len(value) != K:
+                raise ValueError(f"{name} has {len(value)} entries for {K} classes")
+            return list(value)
+        return [value] * K
+
+    methods = []
+    for m in per_class(method, "method"):
+        if m not in ("admm", "newton", METHOD_ADMM, METHOD_NEWTON):
+            raise ValueError("method must be 'admm' or 'newton'")
+        methods.append(METHOD_NEWTON if m in ("newton", METHOD_NEWTON) else METHOD_ADMM)
+    per_settings = [dict(st or {}) for st in per_class(settings, "settings")]
+    table = (MpcqpParams * K)()
+    for k, (p, m, st) in enumerate(zip(params_list, methods, per_settings)):
+        table[k] = to_c_params(p, m, **st)
+        if table[k].horizon != table[0].horizon:
+            raise ValueError(f"class {k} has horizon {table[k].horizon}, class 0 has {table[0].horizon}")
+        if table[k].reproducible != table[0].reproducible:
+            raise ValueError(f"class {k} differs from class 0 in the reproducible flag")
+        if table[k].debug_state:
+            raise ValueError(f"class {k} sets debug_state, which a mixed batch does not write")
+    return table
 
 
 REF_BAD_PATH = -2147483648
@@ -276,6 +315,8 @@ _SYMBOLS = {
     "mpcqp_solve_staged": ([ctypes.c_void_p], ctypes.c_int),
     "mpcqp_solve_served": ([ctypes.c_void_p], ctypes.c_int),
     "mpcqp_set_pairing": ([ctypes.c_void_p, ctypes.c_int], ctypes.c_int),
+    "mpcqp_set_classes": ([ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(MpcqpParams)], ctypes.c_int),
+    "mpcqp_build_mixed": ([ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5, ctypes.c_int),
 }
 
 
@@ -329,6 +370,8 @@ __all__ = [
     "FLEET_REPLAN_ABORTED",
     "CATMULL_MAX_POINTS",
     "to_c_params",
+    "class_table",
+    "BAD_CLASS",
     "REF_BAD_PATH",
     "REF_MAX_POINTS",
     "FLEET_RUNNING",

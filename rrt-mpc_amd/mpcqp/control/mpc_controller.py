@@ -108,6 +108,11 @@ class BatchedMPCController:
 
     ``pairing`` ("auto", "on", "off"): two QPs per wave for horizons N <= 15 (``mpcqp_set_pairing``;
     the same results bit for bit).  "auto" pairs a launch with more QPs than the GPU has wave slots.
+
+    Mixed batches: ``set_classes([params_0, ..., params_{K-1}])`` gives the workspace a table of K
+    parameter blocks of this horizon, and ``solve_batch(..., classes=cls)`` solves QP b under block
+    ``cls[b]`` in the same single launch (``mpcqp_build_mixed``; never paired).  ``solve_one``, the
+    fleet and the swarm keep using the controller's own block.
     """
 
     def __init__(self, params, max_batch: int, *, device=None, method: str = "admm", pairing: str = "auto",
@@ -135,6 +140,7 @@ class BatchedMPCController:
             _lib.check(L.mpcqp_create(ctypes.byref(self._cparams), self.max_batch, self.device.index, ctypes.byref(ws)),
                        "mpcqp_create")
         self._ws = ws
+        self.num_classes = 0
         self.set_pairing(pairing)
         N, B = self.horizon, self.max_batch
         kw = dict(device=self.device)
@@ -159,6 +165,51 @@ class BatchedMPCController:
         _lib.check(self._L.mpcqp_set_pairing(self._ws, _lib.PAIRING_MODES[mode]), "mpcqp_set_pairing")
         self.pairing = mode
 
+    def set_classes(self, params_list, settings=None, *, method=None) -> None:
+        """The parameter blocks ("classes") of mixed batches: ``params_list[k]`` is block k
+        (``mpcqp_set_classes``; synchronous).  ``settings``: one dict of solver settings for all
+        classes or a list with one dict per class, on top of the controller's own settings;
+        ``method``: the controller's by default, or "admm" / "newton", or a list with one per class.
+        ``None`` or an empty list drops the table.  Every block has the controller's horizon."""
+        if not params_list:
+            _lib.check(self._L.mpcqp_set_classes(self._ws, 0, None), "mpcqp_set_classes")
+            self.num_classes = 0
+            return
+        params_list = list(params_list)
+        K = len(params_list)
+        if isinstance(settings, (list, tuple)):
+            if len(settings) != K:
+                raise ValueError(f"settings has {len(settings)} entries for {K} classes")
+            merged = [{**self.settings, **(st or {})} for st in settings]
+        else:
+            merged = {**self.settings, **(settings or {})}
+        table = _lib.class_table(params_list, self.method if method is None else method, merged)
+        if table[0].horizon != self.horizon:
+            raise ValueError(f"the classes have horizon {table[0].horizon}, the controller {self.horizon}")
+        with self._torch.cuda.device(self.device):
+            _lib.check(self._L.mpcqp_set_classes(self._ws, K, table), "mpcqp_set_classes")
+        self.num_classes = K
+
+    def _class_input(self, classes, B):
+        """``classes`` as an int32 device tensor of shape (B,) (a device tensor of that type is used in place)."""
+        torch = self._torch
+        if isinstance(classes, torch.Tensor):
+            if classes.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+                raise ValueError(f"classes must be an integer tensor, got {classes.dtype}")
+            t = classes
+        else:
+            a = np.asarray(classes)
+            if a.dtype.kind not in "iu":
+                raise ValueError(f"classes must be an integer array, got dtype {a.dtype}")
+            # values outside int32 are no class indices: kept out of range (the device reports them per QP)
+            a = np.where((a < 0) | (a > 2**31 - 1), -1, a).astype(np.int32)
+            t = torch.from_numpy(np.ascontiguousarray(a))
+        if tuple(t.shape) != (B,):
+            raise ValueError(f"classes must have shape ({B},), got {tuple(t.shape)}")
+        if t.device != self.device or t.dtype != torch.int32:
+            t = t.to(device=self.device, dtype=torch.int32)
+        return t.contiguous()
+
     def _device_input(self, a, shape, name):
         torch = self._torch
         if isinstance(a, torch.Tensor):
@@ -172,12 +223,18 @@ class BatchedMPCController:
             t = t.reshape(shape)
         return t
 
-    def solve_batch(self, x0, ref, u_prev=None, *, stream=None) -> BatchSolution:
+    def solve_batch(self, x0, ref, u_prev=None, *, stream=None, classes=None) -> BatchSolution:
+        """``classes`` (int array or int32 device tensor of shape (B,)): QP b is solved under block
+        ``classes[b]`` of ``set_classes``; a QP whose index lies outside the table reports status
+        ``_lib.BAD_CLASS`` and none of its other outputs is written.  ``None``: the controller's block."""
         torch = self._torch
         N = self.horizon
         B = int(x0.shape[0])
         if B > self.max_batch:
             raise ValueError(f"batch {B} exceeds max_batch {self.max_batch}")
+        if classes is not None and not self.num_classes:
+            raise ValueError("solve_batch(classes=...) needs a class table: call set_classes first")
+        cls_t = None if classes is None else self._class_input(classes, B)
         x0_t = self._device_input(x0, (B, 4), "x0")
         if len(ref.shape) == 3 and ref.shape[1] > N + 1:  # rows past N are never read (see solve)
             ref = ref[:, : N + 1]
@@ -186,9 +243,14 @@ class BatchedMPCController:
         if stream is None:
             stream = torch.cuda.current_stream(self.device)
         s = ctypes.c_void_p(stream.cuda_stream)
-        self._keep = (x0_t, ref_t, up_t)  # keep inputs alive until the kernels have consumed them
-        _lib.check(self._L.mpcqp_build(self._ws, B, x0_t.data_ptr(), ref_t.data_ptr(),
-                                       None if up_t is None else up_t.data_ptr(), s), "mpcqp_build")
+        self._keep = (x0_t, ref_t, up_t, cls_t)  # keep inputs alive until the kernels have consumed them
+        if cls_t is None:
+            _lib.check(self._L.mpcqp_build(self._ws, B, x0_t.data_ptr(), ref_t.data_ptr(),
+                                           None if up_t is None else up_t.data_ptr(), s), "mpcqp_build")
+        else:
+            _lib.check(self._L.mpcqp_build_mixed(self._ws, B, x0_t.data_ptr(), ref_t.data_ptr(),
+                                                 None if up_t is None else up_t.data_ptr(), cls_t.data_ptr(), s),
+                       "mpcqp_build_mixed")
         _lib.check(self._L.mpcqp_solve(self._ws, B, self._u0.data_ptr(), self._X.data_ptr(), self._U.data_ptr(),
                                        self._status.data_ptr(), self._iters.data_ptr(), self._active.data_ptr(), s),
                    "mpcqp_solve")

@@ -1,0 +1,270 @@
+"""GPU tests of per-QP parameter classes (``mpcqp_set_classes`` / ``mpcqp_build_mixed``): one launch
+for a batch whose QPs do not share one ``mpcqp_params`` block.
+
+A mixed launch runs the iteration of the homogeneous kernels unchanged, with the block read per QP
+from a device table.  So (1) each QP meets the exact oracle under its own block, and (2) -- the
+project's own standard for a kernel variant -- every output of QP b equals, BIT FOR BIT, what a plain
+controller built with block ``cls[b]`` returns for it: in the one-wave kernel (N <= 32, pairing
+ignored), the mid kernel (33..64), the wide kernel (N > 64) and reproducible mode.  Classes may differ
+in solver settings and method too (3).  A class index outside the table is reported per QP and never
+indexes anything (4); the calls keep a build tied to the table it was made with (5).
+"""
+from __future__ import annotations
+
+import numpy as np
+import pytest
+from param_variants import VARIANTS, resolution, variant
+
+pytestmark = pytest.mark.gpu
+
+REL_TOL = 1e-8  # the project's tolerance against the exact oracle (test_gpu_params.py)
+FAIL_NOMINAL = dict(max_iter=1, polish=0, polish_from=0, polish_near=0.0)  # as test_gpu_params.py
+BAD_CLASS = -11
+E_ARG, E_HORIZON, E_STATE = -1, -2, -5
+_OUTS = ("u0", "X", "U", "status", "iters", "active")
+
+
+def _base(N, res=0.8):
+    from mpcqp.config import MPCConfig
+
+    return MPCConfig(horizon=N).to_parameters(res)
+
+
+def _blocks(N):
+    """The nine MPCParameters variants as classes (dt 0.05 / 0.2 and the 14 px wheelbase among them)."""
+    return [variant(_base(N, resolution(name)), name) for name in VARIANTS]
+
+
+def _controller(params, B, **kw):
+    from mpcqp.control.mpc_controller import BatchedMPCController
+
+    return BatchedMPCController(params, B, device="cuda:0", **kw)
+
+
+def _take(sol):
+    import torch
+
+    torch.cuda.synchronize()  # raises if a kernel of the launch faulted
+    return {k: getattr(sol, k).cpu().numpy().copy() for k in _OUTS}
+
+
+def _plain(params, batch, idx, **kw):
+    ctrl = _controller(params, len(idx), **kw)
+    up = None if batch.u_prev is None else batch.u_prev[idx]
+    out = _take(ctrl.solve_batch(batch.x0[idx], batch.ref[idx], up))
+    ctrl.close()
+    return out
+
+
+def _mixed(base, plist, cls, batch, idx=None, *, class_settings=None, class_method=None, **kw):
+    idx = np.arange(batch.size) if idx is None else idx
+    ctrl = _controller(base, len(idx), **kw)
+    ctrl.set_classes(plist, class_settings, method=class_method)
+    out = _take(ctrl.solve_batch(batch.x0[idx], batch.ref[idx], batch.u_prev[idx], classes=np.asarray(cls)[idx]))
+    ctrl.close()
+    return out
+
+
+def _assert_rows_equal(mixed, rows, plain, what):
+    for k in _OUTS:
+        np.testing.assert_array_equal(mixed[k][rows], plain[k], err_msg=f"{what}: {k}")
+
+
+def _rel(a, b):
+    return float(np.abs(a - b).max() / max(1.0, np.abs(b).max()))
+
+
+# ---------------------------------------------------------------------- 1. oracle parity
+@pytest.mark.parametrize("N", [10, 20, 30])
+def test_mixed_batch_matches_exact_oracle_per_class(cuda, N):
+    """The inputs on which test_gpu_params.py shows each variant solves every QP, nine classes in one
+    launch: QP b against solve_exact under block cls[b]."""
+    import mpc_oracle as mo
+    from mpcqp import scenarios
+
+    plist = _blocks(N)
+    batch = scenarios.config3(48, horizon=N, seed=1000 + N)
+    cls = np.arange(batch.size) % len(plist)
+    out = _mixed(_base(N), plist, cls, batch)
+    assert (out["status"] == 1).all(), np.unique(out["status"], return_counts=True)
+    n_active = 0
+    for b in range(batch.size):
+        ex = mo.solve_exact(plist[cls[b]], batch.x0[b], batch.ref[b], batch.u_prev[b])
+        assert ex.converged
+        e = max(_rel(out["U"][b], ex.Umat), _rel(out["X"][b], ex.X), _rel(out["u0"][b], ex.Umat[:, 0]))
+        print(f"N={N} QP {b} class {VARIANTS[cls[b]]}: rel err {e:.3e}")
+        assert e <= REL_TOL, f"N={N} QP {b} ({VARIANTS[cls[b]]}): rel err {e:.3e}"
+        assert np.array_equal(out["active"][b], ex.active), f"N={N} QP {b} ({VARIANTS[cls[b]]}): active set differs"
+        n_active += int((ex.active != 0).any())
+    assert n_active > 0
+
+
+# ---------------------------------------------------------------------- 2. bit identity
+@pytest.mark.parametrize("N,B,kw", [(3, 18, {}), (15, 18, dict(pairing="on")), (16, 18, {}), (20, 18, {}),
+                                    (32, 18, {}), (33, 18, {}), (40, 18, {}), (64, 18, {}), (65, 9, {}),
+                                    (10, 18, dict(reproducible=1))],
+                         ids=["N3", "N15_pairing_on", "N16", "N20", "N32", "N33", "N40", "N64", "N65",
+                              "N10_reproducible"])
+def test_mixed_launch_equals_homogeneous_launches_bitwise(cuda, N, B, kw):
+    """For each class c the QPs with cls == c through a plain controller built with block c: the mixed
+    launch's outputs for those QPs are the same bits (pairing forced on at N = 15 on both sides: the
+    plain side runs two QPs per wave, the mixed launch never does)."""
+    from mpcqp import scenarios
+
+    plist = _blocks(N)
+    batch = scenarios.config3(B, horizon=N, seed=2000 + N)
+    cls = np.arange(B) % len(plist)
+    mixed = _mixed(_base(N), plist, cls, batch, **kw)
+    for c, p in enumerate(plist):
+        rows = np.flatnonzero(cls == c)
+        _assert_rows_equal(mixed, rows, _plain(p, batch, rows, **kw), f"N={N} class {VARIANTS[c]}")
+    assert (mixed["status"] != BAD_CLASS).all()
+    assert (mixed["status"] == 1).any(), mixed["status"]  # solves, not a batch of early exits
+
+
+@pytest.mark.parametrize("N", [12, 20, 40, 65])
+def test_one_class_equals_plain_solve_batch_bitwise(cuda, N):
+    """K = 1 with an all-zero cls (an int32 device tensor, used in place) == the plain solve_batch."""
+    import torch
+    from mpcqp import scenarios
+
+    B = 18 if N <= 64 else 9
+    batch = scenarios.config3(B, horizon=N, seed=3000 + N)
+    p = _base(N)
+    ctrl = _controller(p, B)
+    plain = _take(ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev))
+    ctrl.set_classes([p])
+    cls = torch.zeros(B, dtype=torch.int32, device="cuda:0")
+    one = _take(ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev, classes=cls))
+    ctrl.close()
+    _assert_rows_equal(one, np.arange(B), plain, f"N={N} K=1")
+    assert (plain["status"] == 1).any(), plain["status"]
+
+
+# ---------------------------------------------------------------------- 3. settings per class
+def test_classes_differ_in_solver_settings(cuda):
+    """Class 0 the defaults, class 1 one ADMM iteration without polish: solved and max_iter side by
+    side in one launch, and the class 0 results do not depend on their neighbours."""
+    from mpcqp import scenarios
+
+    N, B = 20, 24
+    p = _base(N)
+    batch = scenarios.config3(B, horizon=N, seed=41)
+    cls = np.arange(B) % 2
+    out = _mixed(p, [p, p], cls, batch, class_settings=[{}, FAIL_NOMINAL])
+    assert (out["status"][cls == 0] == 1).all() and (out["status"][cls == 1] == -2).all(), out["status"]
+    assert (out["iters"][cls == 1, 0] == 1).all() and (out["iters"][cls == 1, 1] == 0).all()
+    _assert_rows_equal(out, np.flatnonzero(cls == 0), _plain(p, batch, np.flatnonzero(cls == 0)), "defaults")
+    _assert_rows_equal(out, np.flatnonzero(cls == 1), _plain(p, batch, np.flatnonzero(cls == 1), **FAIL_NOMINAL),
+                       "one iteration")
+
+
+def test_classes_differ_in_method(cuda):
+    """Class 1 runs method newton (the polish iteration alone) beside ADMM in class 0."""
+    from mpcqp import scenarios
+
+    N, B = 20, 24
+    p = _base(N)
+    batch = scenarios.config3(B, horizon=N, seed=42)
+    cls = np.arange(B) % 2
+    out = _mixed(p, [p, p], cls, batch, class_method=["admm", "newton"])
+    assert (out["status"] == 1).all(), out["status"]
+    assert (out["iters"][cls == 0, 0] > 0).all() and (out["iters"][cls == 1, 0] == 0).all()  # ADMM iterations
+    _assert_rows_equal(out, np.flatnonzero(cls == 0), _plain(p, batch, np.flatnonzero(cls == 0)), "admm")
+    _assert_rows_equal(out, np.flatnonzero(cls == 1), _plain(p, batch, np.flatnonzero(cls == 1), method="newton"),
+                       "newton")
+
+
+# ---------------------------------------------------------------------- 4. bad indices
+@pytest.mark.parametrize("N", [20, 40, 65])
+def test_bad_class_indices_are_reported_per_qp(cuda, N):
+    """cls holding -1, K and 2^31 - 1 among valid entries: those QPs report MPCQP_BAD_CLASS with zero
+    iters and nothing else of theirs is written; every valid QP equals the run without the bad ones.
+    The guard is index arithmetic ahead of every access, so this passes only when it holds."""
+    from mpcqp import scenarios
+
+    B = 12
+    plist = _blocks(N)[:4]
+    K = len(plist)
+    batch = scenarios.config3(B, horizon=N, seed=4000 + N)
+    cls = np.arange(B) % K
+    bad = {2: -1, 5: K, 9: 2**31 - 1}
+    for b, c in bad.items():
+        cls[b] = c
+    good = np.array([b for b in range(B) if b not in bad])
+    ctrl = _controller(_base(N), B)
+    ctrl.set_classes(plist)
+    for buf, fill in ((ctrl._u0, 7.25), (ctrl._X, 7.25), (ctrl._U, 7.25), (ctrl._active, 77), (ctrl._iters, 77)):
+        buf.fill_(fill)
+    out = _take(ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev, classes=cls))  # returns, and the sync is clean
+    ctrl.close()
+    rows = np.array(sorted(bad))
+    assert (out["status"][rows] == BAD_CLASS).all(), out["status"]
+    assert (out["iters"][rows] == 0).all()
+    for k, fill in (("u0", 7.25), ("X", 7.25), ("U", 7.25), ("active", 77)):
+        assert (out[k][rows] == fill).all(), f"{k} of a bad-class QP was written"
+    assert (out["status"][good] == 1).any(), out["status"]
+    _assert_rows_equal(out, good, _mixed(_base(N), plist, cls, batch, good), f"N={N} valid QPs")
+
+
+# ---------------------------------------------------------------------- 5. state rules
+def test_class_state_rules(cuda):
+    import torch
+    from mpcqp import _lib, scenarios
+
+    N, B = 12, 10
+    p = _base(N)
+    plist = _blocks(N)[:3]
+    batch = scenarios.config3(B, horizon=N, seed=5)
+    ctrl = _controller(p, B)
+    L, ws = ctrl._L, ctrl._ws
+    x0, ref, up = (torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0") for a in (batch.x0, batch.ref, batch.u_prev))
+    cls = torch.from_numpy((np.arange(B) % 3).astype(np.int32)).to("cuda:0")
+    outs = (ctrl._u0, ctrl._X, ctrl._U, ctrl._status, ctrl._iters, ctrl._active)
+
+    def build_mixed():
+        return L.mpcqp_build_mixed(ws, B, x0.data_ptr(), ref.data_ptr(), up.data_ptr(), cls.data_ptr(), None)
+
+    def solve():
+        return L.mpcqp_solve(ws, B, *(t.data_ptr() for t in outs), None)
+
+    # no table yet
+    assert build_mixed() == E_STATE
+    assert b"class table" in L.mpcqp_last_error()
+    with pytest.raises(ValueError):
+        ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev, classes=np.zeros(B, np.int32))
+    # a block with another horizon / with debug_state is refused and leaves no table behind
+    wrong = _lib.class_table([_base(N + 1)])
+    assert L.mpcqp_set_classes(ws, 1, wrong) == E_HORIZON
+    dbg = _lib.class_table(plist)
+    dbg[1].debug_state = 1
+    assert L.mpcqp_set_classes(ws, 3, dbg) == E_ARG
+    assert L.mpcqp_set_classes(ws, 3, None) == E_ARG and L.mpcqp_set_classes(ws, -1, dbg) == E_ARG
+    assert build_mixed() == E_STATE
+    # a new table invalidates a mixed build: the solve would run under blocks the build did not see
+    ctrl.set_classes(plist)
+    assert build_mixed() == 0
+    ctrl.set_classes(plist)
+    assert solve() == E_STATE
+    assert build_mixed() == 0 and solve() == 0
+    mixed = _take(ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev, classes=cls))
+    for c in range(3):
+        rows = np.flatnonzero(np.arange(B) % 3 == c)
+        _assert_rows_equal(mixed, rows, _plain(plist[c], batch, rows), f"class {c}")
+    # set_params leaves the table alone (and invalidates the build, as ever)
+    assert build_mixed() == 0
+    ctrl.set_params(p)
+    assert solve() == E_STATE
+    assert build_mixed() == 0 and solve() == 0
+    # a plain build after a mixed one solves under the workspace's own block
+    plain = _take(ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev))
+    _assert_rows_equal(plain, np.arange(B), _plain(p, batch, np.arange(B)), "plain after mixed")
+    # dropping the table
+    ctrl.set_classes(None)
+    assert ctrl.num_classes == 0 and build_mixed() == E_STATE
+    with pytest.raises(ValueError):
+        ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev, classes=cls)
+    again = _take(ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev))
+    _assert_rows_equal(again, np.arange(B), plain, "plain after the table is dropped")
+    torch.cuda.synchronize()
+    ctrl.close()
