@@ -101,65 +101,12 @@ __global__ __launch_bounds__(kWave) void k_wave_ops(const double* __restrict__ i
   out[9 * kWave + lane] = readlane(v, 37);
 }
 
-#ifdef MPCQP_ONLY_N  // development builds: instantiate a single horizon
-#define MPCQP_L(N) ((N) == MPCQP_ONLY_N ? &mpcqp::launch_solve<MPCQP_ONLY_N> : nullptr)
-#else
-#define MPCQP_L(N) &mpcqp::launch_solve<N>
+// The one-wave kernels by horizon (HorizonKernels, mpcqp_common.h): plain data, filled by the objects
+// that hold the kernels before any call can read it.
+mpcqp::HorizonKernels g_kernels[MPCQP_WIDE_MIN_HORIZON] = {};
+#ifdef MPCQP_ONLY_N  // development builds: this translation unit holds the one horizon
+const int kHorizonRegistered = mpcqp::register_horizons<MPCQP_ONLY_N, MPCQP_ONLY_N>();
 #endif
-const mpcqp::launcher_t kLaunchers[MPCQP_WIDE_MIN_HORIZON] = {
-    nullptr,     MPCQP_L(1),  MPCQP_L(2),  MPCQP_L(3),  MPCQP_L(4),  MPCQP_L(5),  MPCQP_L(6),  MPCQP_L(7),
-    MPCQP_L(8),  MPCQP_L(9),  MPCQP_L(10), MPCQP_L(11), MPCQP_L(12), MPCQP_L(13), MPCQP_L(14), MPCQP_L(15),
-    MPCQP_L(16), MPCQP_L(17), MPCQP_L(18), MPCQP_L(19), MPCQP_L(20), MPCQP_L(21), MPCQP_L(22), MPCQP_L(23),
-    MPCQP_L(24), MPCQP_L(25), MPCQP_L(26), MPCQP_L(27), MPCQP_L(28), MPCQP_L(29), MPCQP_L(30), MPCQP_L(31),
-    MPCQP_L(32)};
-#undef MPCQP_L
-#ifdef MPCQP_ONLY_N
-#define MPCQP_M(N) ((N) == MPCQP_ONLY_N ? &mpcqp::launch_solve_mixed<MPCQP_ONLY_N> : nullptr)
-#else
-#define MPCQP_M(N) &mpcqp::launch_solve_mixed<N>
-#endif
-// k_solve_mixed<N>: the one-wave kernel with a parameter block per QP (mpcqp_build_mixed)
-const mpcqp::launcher_t kMixedLaunchers[MPCQP_WIDE_MIN_HORIZON] = {
-    nullptr,     MPCQP_M(1),  MPCQP_M(2),  MPCQP_M(3),  MPCQP_M(4),  MPCQP_M(5),  MPCQP_M(6),  MPCQP_M(7),
-    MPCQP_M(8),  MPCQP_M(9),  MPCQP_M(10), MPCQP_M(11), MPCQP_M(12), MPCQP_M(13), MPCQP_M(14), MPCQP_M(15),
-    MPCQP_M(16), MPCQP_M(17), MPCQP_M(18), MPCQP_M(19), MPCQP_M(20), MPCQP_M(21), MPCQP_M(22), MPCQP_M(23),
-    MPCQP_M(24), MPCQP_M(25), MPCQP_M(26), MPCQP_M(27), MPCQP_M(28), MPCQP_M(29), MPCQP_M(30), MPCQP_M(31),
-    MPCQP_M(32)};
-#undef MPCQP_M
-#ifdef MPCQP_ONLY_N
-#define MPCQP_F(N) ((N) == MPCQP_ONLY_N ? &mpcqp::launch_fleet_loop<MPCQP_ONLY_N> : nullptr)
-#else
-#define MPCQP_F(N) &mpcqp::launch_fleet_loop<N>
-#endif
-const mpcqp::fleet_loop_t kFleetLoops[MPCQP_WIDE_MIN_HORIZON] = {
-    nullptr,     MPCQP_F(1),  MPCQP_F(2),  MPCQP_F(3),  MPCQP_F(4),  MPCQP_F(5),  MPCQP_F(6),  MPCQP_F(7),
-    MPCQP_F(8),  MPCQP_F(9),  MPCQP_F(10), MPCQP_F(11), MPCQP_F(12), MPCQP_F(13), MPCQP_F(14), MPCQP_F(15),
-    MPCQP_F(16), MPCQP_F(17), MPCQP_F(18), MPCQP_F(19), MPCQP_F(20), MPCQP_F(21), MPCQP_F(22), MPCQP_F(23),
-    MPCQP_F(24), MPCQP_F(25), MPCQP_F(26), MPCQP_F(27), MPCQP_F(28), MPCQP_F(29), MPCQP_F(30), MPCQP_F(31),
-    MPCQP_F(32)};
-#undef MPCQP_F
-#ifdef MPCQP_ONLY_N
-#define MPCQP_P(N) ((N) == MPCQP_ONLY_N ? &mpcqp::launch_solve_pair<MPCQP_ONLY_N> : nullptr)
-#else
-#define MPCQP_P(N) &mpcqp::launch_solve_pair<N>
-#endif
-constexpr int kPairMaxHorizon = 15;  // n = 2N <= 30: two QPs per wave
-const mpcqp::pair_launcher_t kPairLaunchers[kPairMaxHorizon + 1] = {
-    nullptr,    MPCQP_P(1),  MPCQP_P(2),  MPCQP_P(3),  MPCQP_P(4),  MPCQP_P(5),  MPCQP_P(6),  MPCQP_P(7),
-    MPCQP_P(8), MPCQP_P(9),  MPCQP_P(10), MPCQP_P(11), MPCQP_P(12), MPCQP_P(13), MPCQP_P(14), MPCQP_P(15)};
-#undef MPCQP_P
-#ifdef MPCQP_ONLY_N
-#define MPCQP_S(N) ((N) == MPCQP_ONLY_N ? &mpcqp::launch_serve<MPCQP_ONLY_N> : nullptr)
-#else
-#define MPCQP_S(N) &mpcqp::launch_serve<N>
-#endif
-const mpcqp::serve_t kServers[MPCQP_WIDE_MIN_HORIZON] = {
-    nullptr,     MPCQP_S(1),  MPCQP_S(2),  MPCQP_S(3),  MPCQP_S(4),  MPCQP_S(5),  MPCQP_S(6),  MPCQP_S(7),
-    MPCQP_S(8),  MPCQP_S(9),  MPCQP_S(10), MPCQP_S(11), MPCQP_S(12), MPCQP_S(13), MPCQP_S(14), MPCQP_S(15),
-    MPCQP_S(16), MPCQP_S(17), MPCQP_S(18), MPCQP_S(19), MPCQP_S(20), MPCQP_S(21), MPCQP_S(22), MPCQP_S(23),
-    MPCQP_S(24), MPCQP_S(25), MPCQP_S(26), MPCQP_S(27), MPCQP_S(28), MPCQP_S(29), MPCQP_S(30), MPCQP_S(31),
-    MPCQP_S(32)};
-#undef MPCQP_S
 
 // per-QP doubles of the solver state buffer (debug state of the one-wave kernel, the workspace
 // of the long-horizon kernel)
@@ -216,13 +163,22 @@ int fail(int code, const std::string& msg) {
   return code;
 }
 bool wide_solve(const mpcqp_params& p) { return p.horizon >= MPCQP_WIDE_MIN_HORIZON || p.reproducible != 0; }
+void register_horizon(int N, const HorizonKernels& k) {
+  if (N >= 1 && N < MPCQP_WIDE_MIN_HORIZON) g_kernels[N] = k;
+}
+// the one-wave kernels of the parameter block's horizon; nullptr when it runs another kernel family
+// (long horizons, reproducible mode) or, for the entry points that keep no debug state, with debug_state
+static const HorizonKernels* one_wave(const mpcqp_params& p, bool debug_ok) {
+  if (wide_solve(p) || (p.debug_state && !debug_ok) || p.horizon < 1) return nullptr;
+  return &g_kernels[p.horizon];
+}
 launcher_t launcher(const mpcqp_params& p) {
   const int horizon = p.horizon;
   if (horizon < 1 || horizon > MPCQP_MAX_HORIZON) return nullptr;
   // fast mode up to MPCQP_MID_MAX_HORIZON: the mid kernel; beyond it, and in reproducible mode, the
   // workgroup kernel that restates the C code operation for operation
   if (wide_solve(p)) return p.reproducible == 0 && horizon <= MPCQP_MID_MAX_HORIZON ? &launch_mid : &launch_solve_wide;
-  return horizon < MPCQP_WIDE_MIN_HORIZON ? kLaunchers[horizon] : nullptr;
+  return one_wave(p, true)->solve;
 }
 int ensure_buffers(mpcqp_ws* ws, bool model, bool state, hipStream_t s) {
   model = model && !ws->model;
@@ -232,28 +188,25 @@ int ensure_buffers(mpcqp_ws* ws, bool model, bool state, hipStream_t s) {
   if (s && hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
     return fail(MPCQP_E_STATE, "the workspace's model/state buffers are allocated at their first use, which "
                                "cannot be inside a stream capture: run the call once uncaptured first");
-  int cur = -1;
-  hipError_t e = hipGetDevice(&cur);
-  if (e == hipSuccess && cur != ws->device) e = hipSetDevice(ws->device);
+  const DeviceGuard dev(ws->device);
+  hipError_t e = dev.err;
   const int N = ws->p.horizon;
   if (e == hipSuccess && model) e = hipMalloc(&ws->model, sizeof(double) * (size_t)model_stride(N) * (size_t)ws->max_batch);
   if (e == hipSuccess && state)
     e = hipMalloc(&ws->state, sizeof(double) * ws_state_stride(N, wide_solve(ws->p)) * (size_t)ws->max_batch);
-  if (cur >= 0 && cur != ws->device) (void)hipSetDevice(cur);
   if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("hipMalloc (workspace buffers): ") + hipGetErrorString(e));
   return MPCQP_OK;
 }
 serve_t server(const mpcqp_params& p) {
-  if (wide_solve(p) || p.debug_state || p.horizon < 1 || p.horizon >= MPCQP_WIDE_MIN_HORIZON) return nullptr;
-  return kServers[p.horizon];
+  const HorizonKernels* k = one_wave(p, false);
+  return k ? k->serve : nullptr;
 }
 bool use_pairs(const mpcqp_ws* ws, int count) {
-  const mpcqp_params& p = ws->p;
   // a mixed build (mpcqp_build_mixed) never pairs: the two halves of a wave would need two parameter
   // blocks, which turns every parameter into a per-lane value
-  if (ws->in_cls) return false;
-  if (wide_solve(p) || p.debug_state || p.horizon < 1 || p.horizon > kPairMaxHorizon || !kPairLaunchers[p.horizon])
-    return false;
+  if (ws->build.cls) return false;
+  const HorizonKernels* k = one_wave(ws->p, false);
+  if (!k || !k->pair) return false;
   if (ws->pairing == MPCQP_PAIR_ON) return true;
   if (ws->pairing == MPCQP_PAIR_OFF) return false;
   // auto: once the QPs outnumber the wave slots (2 per SIMD): below that every QP has a wave of its
@@ -261,8 +214,8 @@ bool use_pairs(const mpcqp_ws* ws, int count) {
   return ws->cus > 0 && count > 8 * ws->cus;
 }
 fleet_loop_t fleet_looper(const mpcqp_params& p) {
-  if (wide_solve(p) || p.debug_state || p.horizon < 1 || p.horizon >= MPCQP_WIDE_MIN_HORIZON) return nullptr;
-  return kFleetLoops[p.horizon];
+  const HorizonKernels* k = one_wave(p, false);
+  return k ? k->loop : nullptr;
 }
 }  // namespace mpcqp
 
@@ -289,24 +242,6 @@ int mpcqp_create(const mpcqp_params* p, int max_batch, int device, mpcqp_ws** ws
   w->p = *p;
   w->max_batch = max_batch;
   w->device = device;
-  w->built_B = -1;
-  w->model = nullptr;
-  w->state = nullptr;
-  w->in_x0 = w->in_ref = w->in_up = nullptr;
-  w->dparams = nullptr;
-  w->dorder = nullptr;
-  w->stage_in = w->stage_in_d = nullptr;
-  w->stage_out = w->stage_out_d = nullptr;
-  w->stage_stream = nullptr;
-  w->serve_box = w->serve_box_d = nullptr;
-  w->serve_seq = 0;
-  w->serve_live = false;
-  w->serve_broken = false;
-  w->serve_fault = 0;
-  w->pairing = MPCQP_PAIR_AUTO;
-  w->dclasses = nullptr;
-  w->n_classes = 0;
-  w->in_cls = nullptr;
   if (hipDeviceGetAttribute(&w->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) w->cus = 0;
   e = hipMalloc(&w->dparams, 2 * sizeof(mpcqp_params));
   if (e == hipSuccess) e = hipMalloc(&w->dorder, sizeof(int32_t) * (size_t)max_batch);
@@ -338,9 +273,7 @@ int mpcqp_set_params(mpcqp_ws* ws, const mpcqp_params* p) {
   // A build belongs to the parameter block it was made with (the fused solve derives its LTV model
   // from the params in effect at solve time, the K1 kernel from those at build time): new params
   // invalidate it, and the next mpcqp_solve needs a new mpcqp_build.
-  ws->built_B = -1;
-  ws->in_x0 = ws->in_ref = ws->in_up = nullptr;
-  ws->in_cls = nullptr;
+  ws->invalidate();
   return MPCQP_OK;
 }
 
@@ -365,9 +298,8 @@ int mpcqp_set_classes(mpcqp_ws* ws, int K, const mpcqp_params* blocks) {
     (void)hipGetLastError();
     return fail(MPCQP_E_STATE, "mpcqp_set_classes inside a stream capture");
   }
-  int cur = -1;
-  hipError_t e = hipGetDevice(&cur);
-  if (e == hipSuccess && cur != ws->device) e = hipSetDevice(ws->device);
+  const mpcqp::DeviceGuard dev(ws->device);
+  hipError_t e = dev.err;
   mpcqp_params* table = nullptr;
   if (e == hipSuccess && K > 0) e = hipMalloc(&table, sizeof(mpcqp_params) * (size_t)K);
   if (e == hipSuccess && K > 0) e = hipMemcpy(table, blocks, sizeof(mpcqp_params) * (size_t)K, hipMemcpyHostToDevice);
@@ -379,13 +311,10 @@ int mpcqp_set_classes(mpcqp_ws* ws, int K, const mpcqp_params* blocks) {
     }
     ws->dclasses = table;
     ws->n_classes = K;
-    ws->built_B = -1;
-    ws->in_x0 = ws->in_ref = ws->in_up = nullptr;
-    ws->in_cls = nullptr;
+    ws->invalidate();
   } else if (table) {
     (void)hipFree(table);
   }
-  if (cur >= 0 && cur != ws->device) (void)hipSetDevice(cur);
   if (e == hipErrorStreamCaptureUnsupported || e == hipErrorStreamCaptureImplicit)
     return fail(MPCQP_E_STATE, "mpcqp_set_classes inside a stream capture");
   if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("class table: ") + hipGetErrorString(e));
@@ -417,31 +346,35 @@ int mpcqp_set_pairing(mpcqp_ws* ws, int mode) {
   return MPCQP_OK;
 }
 
+// K1 of mpcqp_build (cls == nullptr) and mpcqp_build_mixed, after their argument checks; the one place
+// that records a build
+static int build(mpcqp_ws* ws, int B, const double* x0, const double* ref, const double* u_prev, const int32_t* cls,
+                 void* stream) {
+  ws->invalidate();
+  // The one-wave solve builds the model itself (K1 fused into k_solve: the model block never
+  // touches HBM), in a mixed batch under each QP's own block; the K1 kernel runs only for the
+  // long-horizon solve and for inspection builds.
+  const bool fused = !mpcqp::wide_solve(ws->p) && !ws->p.debug_state;
+  if (!fused && B > 0) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = mpcqp::ensure_buffers(ws, true, mpcqp::needs_state(ws->p), s);
+    if (rc) return rc;
+    if (cls)
+      hipLaunchKernelGGL(k_build_mixed, dim3(B), dim3(kWave), 0, s, ws->dclasses, cls, ws->n_classes, B, x0, ref,
+                         u_prev, ws->model);
+    else
+      hipLaunchKernelGGL(k_build, dim3(B), dim3(kWave), 0, s, ws->p, B, x0, ref, u_prev, ws->model);
+    if ((rc = mpcqp::launched(cls ? "k_build_mixed" : "k_build")) != MPCQP_OK) return rc;
+  }
+  if (!fused) x0 = ref = u_prev = nullptr;
+  ws->built(B, x0, ref, u_prev, cls);
+  return MPCQP_OK;
+}
+
 int mpcqp_build(mpcqp_ws* ws, int B, const double* x0, const double* ref, const double* u_prev, void* stream) {
   if (!ws || !x0 || !ref) return fail(MPCQP_E_ARG, "null argument");
   if (B < 0 || B > ws->max_batch) return fail(MPCQP_E_BATCH, "batch exceeds workspace capacity");
-  ws->built_B = B;
-  ws->in_x0 = ws->in_ref = ws->in_up = nullptr;
-  ws->in_cls = nullptr;
-  if (B == 0) return MPCQP_OK;
-  // The one-wave solve builds the model itself (K1 fused into k_solve: the model block never
-  // touches HBM); the K1 kernel runs only for the long-horizon solve and for inspection builds.
-  if (!mpcqp::wide_solve(ws->p) && !ws->p.debug_state) {
-    ws->in_x0 = x0;
-    ws->in_ref = ref;
-    ws->in_up = u_prev;
-    return MPCQP_OK;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int rc = mpcqp::ensure_buffers(ws, true, mpcqp::needs_state(ws->p), s);
-  if (rc) {
-    ws->built_B = -1;
-    return rc;
-  }
-  hipLaunchKernelGGL(k_build, dim3(B), dim3(kWave), 0, s, ws->p, B, x0, ref, u_prev, ws->model);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("k_build launch: ") + hipGetErrorString(e));
-  return MPCQP_OK;
+  return build(ws, B, x0, ref, u_prev, nullptr, stream);
 }
 
 int mpcqp_build_mixed(mpcqp_ws* ws, int B, const double* x0, const double* ref, const double* u_prev,
@@ -450,53 +383,31 @@ int mpcqp_build_mixed(mpcqp_ws* ws, int B, const double* x0, const double* ref, 
   if (!ws->dclasses) return fail(MPCQP_E_STATE, "mpcqp_build_mixed without a class table (mpcqp_set_classes)");
   if (B < 0 || B > ws->max_batch) return fail(MPCQP_E_BATCH, "batch exceeds workspace capacity");
   if (ws->p.debug_state) return fail(MPCQP_E_ARG, "mpcqp_build_mixed needs a workspace without debug_state");
-  ws->built_B = -1;
-  ws->in_x0 = ws->in_ref = ws->in_up = nullptr;
-  ws->in_cls = nullptr;
-  if (B > 0) {
-    if (!mpcqp::wide_solve(ws->p)) {  // the one-wave solve builds each model itself, under the QP's block
-      ws->in_x0 = x0;
-      ws->in_ref = ref;
-      ws->in_up = u_prev;
-    } else {
-      hipStream_t s = static_cast<hipStream_t>(stream);
-      const int rc = mpcqp::ensure_buffers(ws, true, true, s);
-      if (rc) return rc;
-      hipLaunchKernelGGL(k_build_mixed, dim3(B), dim3(kWave), 0, s, ws->dclasses, cls, ws->n_classes, B, x0, ref,
-                         u_prev, ws->model);
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("k_build_mixed launch: ") + hipGetErrorString(e));
-    }
-  }
-  ws->in_cls = cls;
-  ws->built_B = B;
-  return MPCQP_OK;
+  return build(ws, B, x0, ref, u_prev, cls, stream);
 }
 
 int mpcqp_solve(mpcqp_ws* ws, int B, double* u0, double* X, double* U, int32_t* status, int32_t* iters,
                 uint8_t* active, void* stream) {
   if (!ws || !status) return fail(MPCQP_E_ARG, "null argument");
-  if (B != ws->built_B) return fail(MPCQP_E_STATE, "mpcqp_solve B differs from the last mpcqp_build");
+  const mpcqp_ws::Build& built = ws->build;
+  if (!built.valid || B < 0 || B != built.B)
+    return fail(MPCQP_E_STATE, "mpcqp_solve B differs from the last mpcqp_build");
   if (B == 0) return MPCQP_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
   Launch L{&ws->p, B, ws->model, ws->state, u0, X, U, status, iters, active, nullptr};
-  L.x0 = ws->in_x0;
-  L.ref = ws->in_ref;
-  L.u_prev = ws->in_up;
-  if (ws->in_cls) {  // the last build was mpcqp_build_mixed: a parameter block per QP, never paired
+  L.x0 = built.x0;
+  L.ref = built.ref;
+  L.u_prev = built.u_prev;
+  if (built.cls) {  // the last build was mpcqp_build_mixed: a parameter block per QP, never paired
     L.table = ws->dclasses;
-    L.cls = ws->in_cls;
+    L.cls = built.cls;
     L.K = ws->n_classes;
-    // the workgroup-per-QP launchers read L.cls themselves; the one-wave kernel has its own table
-    (mpcqp::wide_solve(ws->p) ? mpcqp::launcher(ws->p) : kMixedLaunchers[ws->p.horizon])(s, L);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("k_solve_mixed launch: ") + hipGetErrorString(e));
-    return MPCQP_OK;
+    // the workgroup-per-QP launchers read L.cls themselves; the one-wave kernel has an entry of its own
+    (mpcqp::wide_solve(ws->p) ? mpcqp::launcher(ws->p) : g_kernels[ws->p.horizon].mixed)(s, L);
+    return mpcqp::launched("k_solve_mixed");
   }
-  if (!(L.ref && mpcqp::use_pairs(ws, B) && kPairLaunchers[ws->p.horizon](s, L))) mpcqp::launcher(ws->p)(s, L);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("k_solve launch: ") + hipGetErrorString(e));
-  return MPCQP_OK;
+  (L.ref && mpcqp::use_pairs(ws, B) ? g_kernels[ws->p.horizon].pair : mpcqp::launcher(ws->p))(s, L);
+  return mpcqp::launched("k_solve");
 }
 
 // ------------------------------------------------------------------ B = 1 path
@@ -517,9 +428,8 @@ int mpcqp_stage(mpcqp_ws* ws, double** in, void** out, int32_t offsets[6]) {
   int32_t off[7];
   stage_offsets(N, off);
   if (!ws->stage_in) {
-    int cur = -1;
-    hipError_t e = hipGetDevice(&cur);
-    if (e == hipSuccess && cur != ws->device) e = hipSetDevice(ws->device);
+    const mpcqp::DeviceGuard dev(ws->device);
+    hipError_t e = dev.err;
     const unsigned fl = hipHostMallocMapped | hipHostMallocCoherent;
     double* hin = nullptr;
     uint8_t* hout = nullptr;
@@ -539,7 +449,6 @@ int mpcqp_stage(mpcqp_ws* ws, double** in, void** out, int32_t offsets[6]) {
     const char* pr = std::getenv("MPCQP_SERVE_PRIORITY");
     const bool dflt = pr && std::strcmp(pr, "default") == 0;
     if (e == hipSuccess) e = hipStreamCreateWithPriority(&st, hipStreamNonBlocking, dflt ? least : greatest);
-    if (cur >= 0 && cur != ws->device) (void)hipSetDevice(cur);
     if (e != hipSuccess) {
       if (hin) (void)hipHostFree(hin);
       if (hout) (void)hipHostFree(hout);
@@ -587,20 +496,25 @@ int mpcqp_solve_staged(mpcqp_ws* ws) {
 static std::mutex g_serve_mu;
 static mpcqp_ws* g_server[64] = {};
 
-// The B = 1 server (k_serve): ends a live server wave (kServeStop) and waits for it.  The caller
-// holds ws->serve_mu.
+// The B = 1 server (k_serve): tells the resident wave to leave (kServeStop) and waits for it; returns
+// the number of the last completed request, after which the next one continues the sequence.  The
+// host's view (serve_seq, serve_live) is the caller's to update.
+static uint32_t serve_dismiss(mpcqp_ws* ws) {
+  auto* box = static_cast<mpcqp::ServeBox*>(ws->serve_box);
+  __atomic_store_n(&box->req, mpcqp::kServeStop, __ATOMIC_RELEASE);
+  (void)hipStreamSynchronize(ws->stage_stream);
+  const uint32_t done = __atomic_load_n(&box->done, __ATOMIC_ACQUIRE);
+  __atomic_store_n(&box->req, done, __ATOMIC_RELEASE);
+  return done;
+}
+// Ends a live server wave.  The caller holds ws->serve_mu.
 static void serve_stop_locked(mpcqp_ws* ws) {
   {
     std::lock_guard<std::mutex> lk(g_serve_mu);
     if (g_server[ws->device & 63] == ws) g_server[ws->device & 63] = nullptr;
   }
   if (!ws->serve_live) return;
-  auto* box = static_cast<mpcqp::ServeBox*>(ws->serve_box);
-  __atomic_store_n(&box->req, mpcqp::kServeStop, __ATOMIC_RELEASE);
-  (void)hipStreamSynchronize(ws->stage_stream);
-  // the next request continues the sequence after the last completed one
-  __atomic_store_n(&box->req, __atomic_load_n(&box->done, __ATOMIC_ACQUIRE), __ATOMIC_RELEASE);
-  ws->serve_seq = __atomic_load_n(&box->done, __ATOMIC_ACQUIRE);
+  ws->serve_seq = serve_dismiss(ws);
   ws->serve_live = false;
 }
 static void serve_stop(mpcqp_ws* ws) {
@@ -638,14 +552,12 @@ int mpcqp_solve_served(mpcqp_ws* ws) {
   if (other) serve_stop_locked(other);
   if (other_lk.owns_lock()) other_lk.unlock();
   if (!ws->serve_box) {
-    int cur = -1;
-    hipError_t e = hipGetDevice(&cur);
-    if (e == hipSuccess && cur != ws->device) e = hipSetDevice(ws->device);
+    const mpcqp::DeviceGuard dev(ws->device);
+    hipError_t e = dev.err;
     void* box = nullptr;
     void* dbox = nullptr;
     if (e == hipSuccess) e = hipHostMalloc(&box, sizeof(mpcqp::ServeBox), hipHostMallocMapped | hipHostMallocCoherent);
     if (e == hipSuccess) e = hipHostGetDevicePointer(&dbox, box, 0);
-    if (cur >= 0 && cur != ws->device) (void)hipSetDevice(cur);
     if (e != hipSuccess) {
       if (box) (void)hipHostFree(box);
       return fail(MPCQP_E_HIP, std::string("B=1 server mailbox: ") + hipGetErrorString(e));
@@ -674,8 +586,7 @@ int mpcqp_solve_served(mpcqp_ws* ws) {
       return fail(MPCQP_E_HIP, "k_serve launch: refused (mpcqp_debug_serve_fault)");
     }
     launch(ws->stage_stream, ws->p, L);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("k_serve launch: ") + hipGetErrorString(e));
+    if (const int rc = mpcqp::launched("k_serve")) return rc;
     ws->serve_live = true;
     return MPCQP_OK;
   };
@@ -742,10 +653,7 @@ int mpcqp_debug_serve_fault(mpcqp_ws* ws, int mode) {
   }
   if (mode == 2) {  // the live wave leaves now, behind the host's back (serve_live stays set)
     if (!ws->serve_live) return fail(MPCQP_E_STATE, "no live server");
-    auto* box = static_cast<mpcqp::ServeBox*>(ws->serve_box);
-    __atomic_store_n(&box->req, mpcqp::kServeStop, __ATOMIC_RELEASE);
-    (void)hipStreamSynchronize(ws->stage_stream);
-    __atomic_store_n(&box->req, __atomic_load_n(&box->done, __ATOMIC_ACQUIRE), __ATOMIC_RELEASE);
+    (void)serve_dismiss(ws);
     return MPCQP_OK;
   }
   if (mode == 3) return ws->serve_live ? 1 : 0;  // query: a server is believed resident
@@ -782,9 +690,7 @@ int mpcqp_debug_stamps(unsigned long long* out32, int reset) {
 int mpcqp_debug_wave_ops(const double* in, double* out, void* stream) {
   if (!in || !out) return fail(MPCQP_E_ARG, "null argument");
   hipLaunchKernelGGL(k_wave_ops, dim3(1), dim3(kWave), 0, static_cast<hipStream_t>(stream), in, out);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("k_wave_ops launch: ") + hipGetErrorString(e));
-  return MPCQP_OK;
+  return mpcqp::launched("k_wave_ops");
 }
 
 }  // extern "C"

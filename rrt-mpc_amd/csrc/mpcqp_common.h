@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <new>
 #include <string>
@@ -448,19 +449,7 @@ struct Launch {
 };
 
 typedef void (*launcher_t)(hipStream_t, const Launch&);
-// two QPs per wave (k_solve_pair, N <= 15, fused K1); returns false where not instantiated
-typedef bool (*pair_launcher_t)(hipStream_t, const Launch&);
-template <int N>
-bool launch_solve_pair(hipStream_t s, const Launch& L);
-// K2a -> K2b -> K2c for horizon N; defined in mpcqp_solve.h, instantiated per horizon in
-// mpcqp_part.hip objects (parallel build) or in mpcqp.hip itself (MPCQP_ONLY_N dev builds).
-template <int N>
-void launch_solve(hipStream_t s, const Launch& L);
-// the one-wave kernel with a parameter block per QP (k_solve_mixed<N>: L.table / L.cls / L.K, fused K1)
-template <int N>
-void launch_solve_mixed(hipStream_t s, const Launch& L);
-// the fused closed loop of a fleet (k_fleet_loop<N>, mpcqp_solve.h; N <= 32, fast mode): `steps`
-// loop steps of every RUNNING vehicle in one launch
+constexpr int kPairMaxHorizon = 15;  // n = 2N <= 30: two QPs per wave
 // The config-5 replan trigger inside the fused loop (mpcqp_swarm_loop): after each step a RUNNING
 // vehicle farther than replan_distance from ref[path_idx], or an ABORTED one, with replans left leaves
 // the loop as MPCQP_FLEET_REPLAN_* with its replanning problem in start_goal.  max_replans = 0: off.
@@ -475,8 +464,6 @@ struct LoopTrigger {
   const int32_t* order = nullptr;
   bool pair = false;  // two vehicles per wave (N <= 15): k_fleet_loop<N, true>
 };
-template <int N>
-void launch_fleet_loop(hipStream_t s, const mpcqp_params* P, const mpcqp_fleet& f, int steps, const LoopTrigger& tr);
 // The B = 1 server (mpcqp_solve_served): one resident wave that solves the QP of the workspace's
 // staging block each time the host raises `req`, then publishes `done`.  In pinned, mapped,
 // coherent host memory; req and done on separate 64-byte lines.
@@ -494,12 +481,23 @@ struct ServeLaunch {
   int32_t off[6];     // output block offsets (u0, X, U, status, iters, active)
   uint64_t idle_ticks;  // s_memrealtime ticks (100 MHz) without a request after which the wave exits
 };
-template <int N>
-void launch_serve(hipStream_t s, const mpcqp_params& p, const ServeLaunch& L);
 typedef void (*serve_t)(hipStream_t, const mpcqp_params&, const ServeLaunch&);
 // nullptr when the parameter block does not run the one-wave kernel; defined in mpcqp.hip
 serve_t server(const mpcqp_params& p);
 typedef void (*fleet_loop_t)(hipStream_t, const mpcqp_params*, const mpcqp_fleet&, int, const LoopTrigger&);
+// The kernels of one horizon of the one-wave family (N < MPCQP_WIDE_MIN_HORIZON; the launch_*<N>
+// templates of mpcqp_solve.h): k_solve, k_solve_mixed (a parameter block per QP), k_solve_pair (two
+// QPs per wave, fused K1; nullptr above kPairMaxHorizon), k_serve (the B = 1 server) and k_fleet_loop
+// (the fused closed loop).  The object that instantiates a horizon registers it from a namespace-scope
+// initialiser (register_horizons, mpcqp_solve.h); an all-null entry is a horizon not compiled in.
+struct HorizonKernels {
+  launcher_t solve, mixed, pair;
+  serve_t serve;
+  fleet_loop_t loop;
+};
+// fills entry N of the table in mpcqp.hip (constant-initialised, so the order of the objects'
+// initialisers does not matter)
+void register_horizon(int N, const HorizonKernels& k);
 // nullptr when the parameter block does not run the one-wave kernel; defined in mpcqp.hip
 fleet_loop_t fleet_looper(const mpcqp_params& p);
 // k_solve_pair / k_fleet_loop<N, true> for `count` QPs or vehicles of this workspace's launch?
@@ -526,55 +524,85 @@ bool wide_solve(const mpcqp_params& p);
 launcher_t launcher(const mpcqp_params& p);
 // records msg as mpcqp_last_error() of the calling thread and returns code; defined in mpcqp.hip
 int fail(int code, const std::string& msg);
+// after a kernel launch: MPCQP_OK, or MPCQP_E_HIP with "<what> launch: <HIP's error>"
+inline int launched(const char* what) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
+  return MPCQP_OK;
+}
+// Makes `device` current for a scope and restores the caller's device on exit (only when one was
+// read and differs).  err: the first failure of the two calls.
+struct DeviceGuard {
+  int device, cur = -1;
+  hipError_t err;
+  explicit DeviceGuard(int dev) : device(dev) {
+    err = hipGetDevice(&cur);
+    if (err == hipSuccess && cur != device) err = hipSetDevice(device);
+  }
+  ~DeviceGuard() {
+    if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
+  }
+  DeviceGuard(const DeviceGuard&) = delete;
+  DeviceGuard& operator=(const DeviceGuard&) = delete;
+};
 }  // namespace mpcqp
 
 // Workspace of one device: parameter block + per-QP model (K1 output) and solver state.
 struct mpcqp_ws {
   mpcqp_params p;
-  int max_batch;
-  int device;
-  int built_B;
+  int max_batch = 0;
+  int device = 0;
+  // What the workspace holds for mpcqp_solve: the batch of the last successful mpcqp_build /
+  // mpcqp_build_mixed; its inputs when the model is built inside the solve (fused K1, else null); its
+  // class indices when it was a mixed build (else null).  New parameters, a new class table and every
+  // fleet or swarm call that uses the workspace invalidate it.  built() and invalidate() are the only
+  // writers.
+  struct Build {
+    bool valid = false;
+    int B = 0;
+    const double *x0 = nullptr, *ref = nullptr, *u_prev = nullptr;
+    const int32_t* cls = nullptr;
+  };
+  Build build;
+  void invalidate() { build = Build{}; }
+  void built(int B, const double* x0, const double* ref, const double* u_prev, const int32_t* cls) {
+    build = Build{true, B, x0, ref, u_prev, cls};
+  }
   // per-QP model (K1 output) and solver state, allocated by ensure_buffers at the first call that
   // needs them: the fused one-wave solve builds the model on chip and keeps the scaled problem
   // there, so a workspace that only runs it holds neither (22 KB per QP at N = 20)
-  double* model;
-  double* state;
-  // the inputs of the last mpcqp_build when the model is built inside the solve (fused K1)
-  const double* in_x0;
-  const double* in_ref;
-  const double* in_up;
+  double* model = nullptr;
+  double* state = nullptr;
   // device copies of the parameter blocks of the last mpcqp_fleet_loop (nominal, relaxed): the fused
   // loop selects its block per solve, which a kernel argument cannot be (the compiler copies a
   // run-time-selected argument block to scratch); written by a kernel on the launch stream
-  mpcqp_params* dparams;
+  mpcqp_params* dparams = nullptr;
   // the fused loop's dispatch order (max_batch vehicles), written by k_fleet_order on the stream
-  int32_t* dorder;
+  int32_t* dorder = nullptr;
   // the B = 1 path (mpcqp_stage / mpcqp_solve_staged): mapped host blocks and a private stream
-  double* stage_in;      // host address (x0 | ref | u_prev)
-  double* stage_in_d;    // its device address
-  uint8_t* stage_out;    // host address (u0 | X | U | status | iters | active)
-  uint8_t* stage_out_d;  // its device address
-  hipStream_t stage_stream;
+  double* stage_in = nullptr;      // host address (x0 | ref | u_prev)
+  double* stage_in_d = nullptr;    // its device address
+  uint8_t* stage_out = nullptr;    // host address (u0 | X | U | status | iters | active)
+  uint8_t* stage_out_d = nullptr;  // its device address
+  hipStream_t stage_stream = nullptr;
   // the B = 1 server: mailbox (host / device address), sequence number, a server kernel enqueued
-  void* serve_box;
-  void* serve_box_d;
-  uint32_t serve_seq;
-  bool serve_live;
-  bool serve_broken;  // a request went unanswered (30 s): the workspace refuses B = 1 requests
-  int serve_fault;    // mpcqp_debug_serve_fault: 1 = refuse the next server launch
+  void* serve_box = nullptr;
+  void* serve_box_d = nullptr;
+  uint32_t serve_seq = 0;
+  bool serve_live = false;
+  bool serve_broken = false;  // a request went unanswered (30 s): the workspace refuses B = 1 requests
+  int serve_fault = 0;        // mpcqp_debug_serve_fault: 1 = refuse the next server launch
   std::chrono::steady_clock::time_point serve_last;  // the last completed request (host clock)
   // guards the server fields above: held by mpcqp_solve_served for its whole call, by set_params /
   // destroy around their stop, and try-locked by another workspace's served call that would stop this
   // workspace's wave (it skips the stop while this one is busy)
   std::mutex serve_mu;
   // two QPs per wave for N <= 15 (MPCQP_PAIR_*, mpcqp_set_pairing)
-  int pairing;
-  int cus;  // the device's compute units (queried once at mpcqp_create; 0 if unknown)
-  // per-QP parameter classes (mpcqp_set_classes): the device table of n_classes blocks, and the class
-  // indices of the last build when that was an mpcqp_build_mixed (nullptr after a plain mpcqp_build)
-  mpcqp_params* dclasses;
-  int n_classes;
-  const int32_t* in_cls;
+  int pairing = MPCQP_PAIR_AUTO;
+  int cus = 0;  // the device's compute units (queried once at mpcqp_create; 0 if unknown)
+  // per-QP parameter classes (mpcqp_set_classes): the device table of n_classes blocks
+  mpcqp_params* dclasses = nullptr;
+  int n_classes = 0;
 };
 
 namespace mpcqp {
@@ -589,4 +617,10 @@ int ensure_buffers(mpcqp_ws* ws, bool model, bool state, hipStream_t s);
 inline bool needs_state(const mpcqp_params& p) { return wide_solve(p) || p.debug_state != 0; }
 // the stepped fleet's buffers (k_fleet_build writes the models; mpcqp_fleet.hip), before a capture
 int fleet_buffers(mpcqp_ws* nominal, mpcqp_ws* relaxed, hipStream_t s);
+// One captured step, replayed `steps` times (mpcqp_fleet.hip; the stepped fleet and swarm): waits on
+// the caller's stream, runs `prepare` outside the capture, captures step(s2) on a private stream,
+// replays it, orders the caller's stream after the replays and waits for them.  `what` ("fleet",
+// "swarm") names the caller in the "<what> graph setup / replay" errors.
+int replay_graph(const char* what, hipStream_t user, int steps, const std::function<int()>& prepare,
+                 const std::function<int(hipStream_t)>& step);
 }  // namespace mpcqp

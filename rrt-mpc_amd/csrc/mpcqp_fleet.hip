@@ -175,10 +175,8 @@ int enqueue_step(mpcqp_ws* nom, mpcqp_ws* rel, const mpcqp_fleet* f, hipStream_t
   if (!solve) return fail(MPCQP_E_HORIZON, "horizon not compiled into this build");
   const int rc = mpcqp::fleet_buffers(nom, rel, s);
   if (rc) return rc;
-  nom->built_B = -1;  // the fleet overwrites the models: a later mpcqp_solve needs its own build
-  rel->built_B = -1;
-  nom->in_x0 = nom->in_ref = nom->in_up = nullptr;
-  rel->in_x0 = rel->in_ref = rel->in_up = nullptr;
+  nom->invalidate();  // the fleet overwrites the models: a later mpcqp_solve needs its own build
+  rel->invalidate();
   hipLaunchKernelGGL(k_fleet_build, dim3(V), dim3(kWave), 0, s, nom->p, *f, 0, nom->model);
   solve(s, Launch{&nom->p, V, nom->model, nom->state, f->u0, f->X, nullptr, f->status, nullptr, nullptr, f->mask});
   hipLaunchKernelGGL(k_fleet_build, dim3(V), dim3(kWave), 0, s, rel->p, *f, 1, rel->model);
@@ -186,57 +184,14 @@ int enqueue_step(mpcqp_ws* nom, mpcqp_ws* rel, const mpcqp_fleet* f, hipStream_t
                   nullptr, f->mask + V});
   hipLaunchKernelGGL(k_fleet_advance, dim3((V + kWave - 1) / kWave), dim3(kWave), 0, s, nom->p.dt,
                      nom->p.wheelbase_px, *f);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("fleet step launch: ") + hipGetErrorString(e));
-  return MPCQP_OK;
+  return mpcqp::launched("fleet step");
 }
-
-#define HIP_OR_FAIL(call)                                                                    \
-  do {                                                                                       \
-    hipError_t e_ = (call);                                                                  \
-    if (e_ != hipSuccess) return fail(MPCQP_E_HIP, std::string(#call ": ") + hipGetErrorString(e_)); \
-  } while (0)
 
 // One captured step, replayed `steps` times on a private stream ordered against the caller's.
 int run_graph(mpcqp_ws* nom, mpcqp_ws* rel, const mpcqp_fleet* f, int steps, hipStream_t user) {
-  hipStream_t s2 = nullptr;
-  hipEvent_t ev = nullptr;
-  hipGraph_t g = nullptr;
-  hipGraphExec_t ex = nullptr;
-  int rc = MPCQP_OK;
-  auto cleanup = [&]() {
-    if (ex) (void)hipGraphExecDestroy(ex);
-    if (g) (void)hipGraphDestroy(g);
-    if (ev) (void)hipEventDestroy(ev);
-    if (s2) (void)hipStreamDestroy(s2);
-  };
-  hipError_t e = hipStreamCreateWithFlags(&s2, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventRecord(ev, user);
-  if (e == hipSuccess) e = hipStreamWaitEvent(s2, ev, 0);
-  if (e == hipSuccess && (rc = mpcqp::fleet_buffers(nom, rel, user)) != MPCQP_OK) {  // outside the capture
-    cleanup();
-    return rc;
-  }
-  if (e == hipSuccess) e = hipStreamBeginCapture(s2, hipStreamCaptureModeThreadLocal);
-  if (e != hipSuccess) {
-    cleanup();
-    return fail(MPCQP_E_HIP, std::string("fleet graph setup: ") + hipGetErrorString(e));
-  }
-  rc = enqueue_step(nom, rel, f, s2);
-  e = hipStreamEndCapture(s2, &g);
-  if (rc == MPCQP_OK && e != hipSuccess) rc = fail(MPCQP_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-  if (rc == MPCQP_OK) {
-    e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-    for (int i = 0; e == hipSuccess && i < steps; ++i) e = hipGraphLaunch(ex, s2);
-    if (e == hipSuccess) e = hipEventRecord(ev, s2);
-    if (e == hipSuccess) e = hipStreamWaitEvent(user, ev, 0);
-    // the replays must finish before the graph and its stream are released
-    if (e == hipSuccess) e = hipStreamSynchronize(s2);
-    if (e != hipSuccess) rc = fail(MPCQP_E_HIP, std::string("fleet graph replay: ") + hipGetErrorString(e));
-  }
-  cleanup();
-  return rc;
+  return mpcqp::replay_graph(
+      "fleet", user, steps, [&] { return mpcqp::fleet_buffers(nom, rel, user); },
+      [&](hipStream_t s2) { return enqueue_step(nom, rel, f, s2); });
 }
 
 }  // namespace
@@ -259,6 +214,48 @@ int fleet_buffers(mpcqp_ws* nominal, mpcqp_ws* relaxed, hipStream_t s) {
   return rc;
 }
 
+int replay_graph(const char* what, hipStream_t user, int steps, const std::function<int()>& prepare,
+                 const std::function<int(hipStream_t)>& step) {
+  hipStream_t s2 = nullptr;
+  hipEvent_t ev = nullptr;
+  hipGraph_t g = nullptr;
+  hipGraphExec_t ex = nullptr;
+  int rc = MPCQP_OK;
+  auto cleanup = [&]() {
+    if (ex) (void)hipGraphExecDestroy(ex);
+    if (g) (void)hipGraphDestroy(g);
+    if (ev) (void)hipEventDestroy(ev);
+    if (s2) (void)hipStreamDestroy(s2);
+  };
+  hipError_t e = hipStreamCreateWithFlags(&s2, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventRecord(ev, user);
+  if (e == hipSuccess) e = hipStreamWaitEvent(s2, ev, 0);
+  if (e == hipSuccess && (rc = prepare()) != MPCQP_OK) {  // outside the capture
+    cleanup();
+    return rc;
+  }
+  if (e == hipSuccess) e = hipStreamBeginCapture(s2, hipStreamCaptureModeThreadLocal);
+  if (e != hipSuccess) {
+    cleanup();
+    return fail(MPCQP_E_HIP, std::string(what) + " graph setup: " + hipGetErrorString(e));
+  }
+  rc = step(s2);
+  e = hipStreamEndCapture(s2, &g);
+  if (rc == MPCQP_OK && e != hipSuccess) rc = fail(MPCQP_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
+  if (rc == MPCQP_OK) {
+    e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
+    for (int i = 0; e == hipSuccess && i < steps; ++i) e = hipGraphLaunch(ex, s2);
+    if (e == hipSuccess) e = hipEventRecord(ev, s2);
+    if (e == hipSuccess) e = hipStreamWaitEvent(user, ev, 0);
+    // the replays must finish before the graph and its stream are released
+    if (e == hipSuccess) e = hipStreamSynchronize(s2);
+    if (e != hipSuccess) rc = fail(MPCQP_E_HIP, std::string(what) + " graph replay: " + hipGetErrorString(e));
+  }
+  cleanup();
+  return rc;
+}
+
 // the fused loop with the swarm's trigger (tr.max_replans > 0, mpcqp_swarm_loop) or without; nullptr
 // looper (mid / long horizons, reproducible or debug mode): *fused = false, nothing enqueued
 int enqueue_fleet_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, int steps, const LoopTrigger& tr,
@@ -266,10 +263,8 @@ int enqueue_fleet_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* 
   const mpcqp::fleet_loop_t loop = mpcqp::fleet_looper(nominal->p);
   *fused = loop && mpcqp::fleet_looper(relaxed->p) == loop;
   if (!*fused) return MPCQP_OK;
-  nominal->built_B = -1;  // as mpcqp_fleet_step: a later mpcqp_solve needs its own build
-  relaxed->built_B = -1;
-  nominal->in_x0 = nominal->in_ref = nominal->in_up = nullptr;
-  relaxed->in_x0 = relaxed->in_ref = relaxed->in_up = nullptr;
+  nominal->invalidate();  // as mpcqp_fleet_step: a later mpcqp_solve needs its own build
+  relaxed->invalidate();
   hipLaunchKernelGGL(k_store_params, dim3(1), dim3(kWave), 0, s, nominal->p, relaxed->p, nominal->dparams);
   LoopTrigger tro = tr;
   // longest first only when the vehicles outnumber the wave slots (2 per SIMD): with every vehicle
@@ -280,9 +275,7 @@ int enqueue_fleet_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* 
   }
   tro.pair = mpcqp::use_pairs(nominal, f->vehicles);
   loop(s, nominal->dparams, *f, steps, tro);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("k_fleet_loop launch: ") + hipGetErrorString(e));
-  return MPCQP_OK;
+  return launched("k_fleet_loop");
 }
 }  // namespace mpcqp
 

@@ -47,9 +47,7 @@ int mpcqp_inflate(int B, int height, int width, int radius_px, const uint8_t* oc
   dim3 grid((width + 15) / 16, (height + 15) / 16, B);
   hipLaunchKernelGGL(k_inflate, grid, dim3(256), 0, static_cast<hipStream_t>(stream), B, height, width, radius_px,
                      occupancy, out);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("k_inflate launch: ") + hipGetErrorString(e));
-  return MPCQP_OK;
+  return mpcqp::launched("k_inflate");
 }
 
 }  // extern "C"

@@ -53,9 +53,7 @@ int mpcqp_build_reference(int V, const double* pts, const int32_t* path_off, int
   }
   hipLaunchKernelGGL(k_build_reference, dim3(V), dim3(kWave), lds, static_cast<hipStream_t>(stream), V, pts,
                      path_off, cap, desired_speed, horizon, dt, ref_stride, ref, ref_len);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("k_build_reference launch: ") + hipGetErrorString(e));
-  return MPCQP_OK;
+  return mpcqp::launched("k_build_reference");
 }
 
 }  // extern "C"

@@ -87,9 +87,7 @@ int mpcqp_plan_math(int op, int n, const double* a, const double* b, double* out
   if (!a || !b || !out0 || (op == 1 && (!out1 || !out2))) return fail(MPCQP_E_ARG, "null argument");
   hipLaunchKernelGGL(k_plan_math, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), op, n, a, b,
                      out0, out1, out2);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("k_plan_math launch: ") + hipGetErrorString(e));
-  return MPCQP_OK;
+  return mpcqp::launched("k_plan_math");
 }
 
 int mpcqp_rrt_paths(const mpcqp_rrt_params* p, int V, int prune, const uint8_t* occupancy, const double* nodes,
@@ -111,9 +109,7 @@ int mpcqp_rrt_paths(const mpcqp_rrt_params* p, int V, int prune, const uint8_t* 
   }
   hipLaunchKernelGGL(k_rrt_paths, dim3(V), dim3(kPlanThreads), lds, static_cast<hipStream_t>(stream), *p, V,
                      prune, occupancy, nodes, count, meta, raw, raw_len, pruned, pruned_len);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("k_rrt_paths launch: ") + hipGetErrorString(e));
-  return MPCQP_OK;
+  return mpcqp::launched("k_rrt_paths");
 }
 
 int mpcqp_rrt_plan(const mpcqp_rrt_params* p, int V, const uint8_t* occupancy, const double* start_goal,
@@ -138,9 +134,7 @@ int mpcqp_rrt_plan(const mpcqp_rrt_params* p, int V, const uint8_t* occupancy, c
   }
   hipLaunchKernelGGL(k_rrt_plan, dim3(V), dim3(kPlanThreads), lds_r, static_cast<hipStream_t>(stream), *p, V,
                      occupancy, start_goal, samples, rng_state, nodes, count, meta);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("k_rrt_plan launch: ") + hipGetErrorString(e));
-  return MPCQP_OK;
+  return mpcqp::launched("k_rrt_plan");
 }
 
 }  // extern "C"

@@ -2183,18 +2183,24 @@ void launch_fleet_loop(hipStream_t s, const mpcqp_params* P, const mpcqp_fleet& 
   }
   hipLaunchKernelGGL(k_fleet_loop<N>, dim3(f.vehicles), dim3(kWave), 0, s, P, f, steps, tr);
 }
-// two QPs per wave (N <= 15, fused K1, no debug state); false: not available for this launch
+// two QPs per wave (N <= kPairMaxHorizon, fused K1, no debug state)
 template <int N>
-bool launch_solve_pair(hipStream_t s, const Launch& L) {
-  if constexpr (2 * N <= 30) {
-    hipLaunchKernelGGL(k_solve_pair<N>, dim3((L.B + 1) / 2), dim3(kWave), 0, s, *L.p, L.B, L.mask, L.x0, L.ref,
-                       L.u_prev, L.u0, L.X, L.U, L.st, L.it, L.ac);
-    return true;
-  } else {
-    (void)s;
-    (void)L;
-    return false;
-  }
+void launch_solve_pair(hipStream_t s, const Launch& L) {
+  static_assert(N <= kPairMaxHorizon, "a half-wave holds n = 2N <= 30 variables");
+  hipLaunchKernelGGL(k_solve_pair<N>, dim3((L.B + 1) / 2), dim3(kWave), 0, s, *L.p, L.B, L.mask, L.x0, L.ref,
+                     L.u_prev, L.u0, L.X, L.U, L.st, L.it, L.ac);
+}
+
+// Registers the kernels of horizons LO..HI with the table in mpcqp.hip; called from a namespace-scope
+// initialiser of the object that is to hold them (taking the launchers' addresses there is what
+// instantiates the kernels).  A new per-horizon entry point: a member of HorizonKernels, and here.
+template <int LO, int HI>
+int register_horizons() {
+  HorizonKernels k{&launch_solve<LO>, &launch_solve_mixed<LO>, nullptr, &launch_serve<LO>, &launch_fleet_loop<LO>};
+  if constexpr (LO <= kPairMaxHorizon) k.pair = &launch_solve_pair<LO>;
+  register_horizon(LO, k);
+  if constexpr (LO < HI) return register_horizons<LO + 1, HI>();
+  return 0;
 }
 
 }  // namespace mpcqp

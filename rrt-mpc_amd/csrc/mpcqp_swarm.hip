@@ -226,9 +226,7 @@ int enqueue_replan(const mpcqp_fleet* f, const mpcqp_swarm* s, hipStream_t st, b
   hipLaunchKernelGGL(k_swarm_smooth, dim3(V), dim3(kWave), lc, st, fv, sv);
   hipLaunchKernelGGL(k_swarm_refbuild, dim3(V), dim3(kWave), lr, st, fv, sv);
   hipLaunchKernelGGL(k_swarm_commit, dim3(V), dim3(kWave), 0, st, fv, sv);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("swarm replan launch: ") + hipGetErrorString(e));
-  return MPCQP_OK;
+  return mpcqp::launched("swarm replan");
 }
 
 }  // namespace
@@ -249,9 +247,7 @@ int mpcqp_catmull_rom(int V, const double* in, const int32_t* in_len, int in_str
   if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
   hipLaunchKernelGGL(k_catmull_rom, dim3(V), dim3(kWave), lds, static_cast<hipStream_t>(stream), V, in, in_len,
                      in_stride, samples, alpha, dedupe_tol, out, out_len, out_stride);
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("k_catmull_rom launch: ") + hipGetErrorString(e));
-  return MPCQP_OK;
+  return mpcqp::launched("k_catmull_rom");
 }
 
 int mpcqp_swarm_step(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s, void* stream) {
@@ -304,44 +300,13 @@ int mpcqp_swarm_run(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, 
     }
     return MPCQP_OK;
   }
-  hipStream_t s2 = nullptr;
-  hipEvent_t ev = nullptr;
-  hipGraph_t g = nullptr;
-  hipGraphExec_t ex = nullptr;
-  auto cleanup = [&]() {
-    if (ex) (void)hipGraphExecDestroy(ex);
-    if (g) (void)hipGraphDestroy(g);
-    if (ev) (void)hipEventDestroy(ev);
-    if (s2) (void)hipStreamDestroy(s2);
-  };
-  hipError_t e = hipStreamCreateWithFlags(&s2, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventRecord(ev, user);
-  if (e == hipSuccess) e = hipStreamWaitEvent(s2, ev, 0);
-  if (e == hipSuccess && ((rc = set_replan_attrs(s)) != MPCQP_OK ||  // outside the capture
-                          (rc = mpcqp::fleet_buffers(nominal, relaxed, user)) != MPCQP_OK)) {
-    cleanup();
-    return rc;
-  }
-  if (e == hipSuccess) e = hipStreamBeginCapture(s2, hipStreamCaptureModeThreadLocal);
-  if (e != hipSuccess) {
-    cleanup();
-    return fail(MPCQP_E_HIP, std::string("swarm graph setup: ") + hipGetErrorString(e));
-  }
-  rc = mpcqp_swarm_step(nominal, relaxed, f, s, s2);
-  e = hipStreamEndCapture(s2, &g);
-  if (rc == MPCQP_OK && e != hipSuccess)
-    rc = fail(MPCQP_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-  if (rc == MPCQP_OK) {
-    e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-    for (int i = 0; e == hipSuccess && i < steps; ++i) e = hipGraphLaunch(ex, s2);
-    if (e == hipSuccess) e = hipEventRecord(ev, s2);
-    if (e == hipSuccess) e = hipStreamWaitEvent(user, ev, 0);
-    if (e == hipSuccess) e = hipStreamSynchronize(s2);
-    if (e != hipSuccess) rc = fail(MPCQP_E_HIP, std::string("swarm graph replay: ") + hipGetErrorString(e));
-  }
-  cleanup();
-  return rc;
+  return mpcqp::replay_graph(
+      "swarm", user, steps,
+      [&] {
+        const int attrs = set_replan_attrs(s);
+        return attrs != MPCQP_OK ? attrs : mpcqp::fleet_buffers(nominal, relaxed, user);
+      },
+      [&](hipStream_t s2) { return mpcqp_swarm_step(nominal, relaxed, f, s, s2); });
 }
 
 }  // extern "C"

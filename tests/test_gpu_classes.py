@@ -268,3 +268,76 @@ def test_class_state_rules(cuda):
     _assert_rows_equal(again, np.arange(B), plain, "plain after the table is dropped")
     torch.cuda.synchronize()
     ctrl.close()
+
+
+_FILLS = (("_u0", 7.25), ("_X", 7.25), ("_U", 7.25), ("_status", 77), ("_iters", 77), ("_active", 77))
+
+
+def _raw_solve(ctrl, B):
+    """mpcqp_solve on the controller's own output buffers, as the C caller sees it."""
+    return ctrl._L.mpcqp_solve(ctrl._ws, B, *(getattr(ctrl, name).data_ptr() for name, _ in _FILLS), None)
+
+
+def test_solve_without_a_valid_build_is_refused(cuda, golden):
+    """mpcqp_solve answers MPCQP_E_STATE, and launches nothing, when the workspace holds no valid
+    build: B = -1 on a fresh workspace (once the value that stood for "no build"), and any B after a
+    fleet step has used the workspace of an earlier mpcqp_build."""
+    import ctypes
+
+    import torch
+    from mpcqp import scenarios
+    from test_gpu_fleet import _tracker, _varied_fleet
+
+    N, V = 3, 2
+    g, paths, starts, goals = _varied_fleet(golden, V)
+    ft = _tracker(N, V, 128, 4, use_graph=False)
+    ctrl = ft._nominal
+    L, ws = ctrl._L, ctrl._ws
+    for name, fill in _FILLS:
+        getattr(ctrl, name).fill_(fill)
+    assert _raw_solve(ctrl, -1) == E_STATE
+    assert b"mpcqp_build" in L.mpcqp_last_error()
+    batch = scenarios.config3(V, horizon=N, seed=8)
+    x0, ref, up = (torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0") for a in (batch.x0, batch.ref, batch.u_prev))
+    assert L.mpcqp_build(ws, V, x0.data_ptr(), ref.data_ptr(), up.data_ptr(), None) == 0
+    ft.reset_from_plans(paths, starts, goals)
+    assert L.mpcqp_fleet_step(ws, ft._relaxed._ws, ctypes.byref(ft._fleet), None) == 0
+    assert _raw_solve(ctrl, -1) == E_STATE
+    assert _raw_solve(ctrl, V) == E_STATE
+    torch.cuda.synchronize()
+    assert (ft.buffers()["mask"][0].cpu().numpy() == 1).all()  # the fleet step itself ran
+    for name, fill in _FILLS:
+        assert (getattr(ctrl, name).cpu().numpy() == fill).all(), f"{name} was written"
+    ft.close()
+
+
+def test_fused_loop_after_a_mixed_build_equals_fresh_workspaces(cuda, golden):
+    """A fleet call invalidates the whole build record, the class indices of an mpcqp_build_mixed
+    included: the fused loop (pairing forced on, three vehicles: a half-empty last wave) on workspaces
+    whose nominal one last held a mixed build leaves every fleet buffer as on fresh workspaces, bit for
+    bit, and mpcqp_solve afterwards needs a new build."""
+    import torch
+    from mpcqp import scenarios
+    from test_gpu_fleet import _tracker, _varied_fleet
+
+    N, V, steps = 3, 3, 4
+    g, paths, starts, goals = _varied_fleet(golden, V)
+    batch = scenarios.config3(V, horizon=N, seed=9)
+    bufs = []
+    for mixed_first in (False, True):
+        ft = _tracker(N, V, 128, steps, fused=True)
+        for c in (ft._nominal, ft._relaxed):
+            c.set_pairing("on")
+        if mixed_first:
+            ft._nominal.set_classes(_blocks(N)[:2])
+            out = _take(ft._nominal.solve_batch(batch.x0, batch.ref, batch.u_prev, classes=np.arange(V) % 2))
+            assert (out["status"] != BAD_CLASS).all() and (out["status"] == 1).any(), out["status"]
+        ft.reset_from_plans(paths, starts, goals)
+        ft.step(steps)
+        torch.cuda.synchronize()
+        bufs.append({k: t.cpu().numpy().copy() for k, t in ft.buffers().items()})
+        assert _raw_solve(ft._nominal, V) == E_STATE
+        ft.close()
+    assert (bufs[0]["steps"] > 0).any(), bufs[0]["steps"]  # the loop stepped
+    for k in bufs[0]:
+        np.testing.assert_array_equal(bufs[0][k], bufs[1][k], err_msg=k)

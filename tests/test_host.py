@@ -422,6 +422,27 @@ def test_argument_checks_without_a_device():
     assert L.mpcqp_stage(None, ctypes.byref(hin), ctypes.byref(hout), offs) == E_ARG
 
 
+def test_every_horizon_is_compiled_in():
+    """Every object that holds one-wave kernels registered its horizons with the library's kernel
+    table: for N = 1..64, mpcqp_create with default parameters never answers MPCQP_E_HORIZON.  Without
+    a device it fails later, at hipSetDevice (MPCQP_E_HIP); with one it succeeds."""
+    from mpcqp.config import MPCConfig
+
+    _lib_mod = _binding()
+    L = _lib_mod.lib()
+    OK, E_HORIZON, E_HIP = 0, -2, -4
+    for N in range(1, 65):
+        cp = _lib_mod.to_c_params(MPCConfig(horizon=N).to_parameters(0.8))
+        ws = ctypes.c_void_p()
+        rc = L.mpcqp_create(ctypes.byref(cp), 1, 0, ctypes.byref(ws))
+        assert rc != E_HORIZON, (N, L.mpcqp_last_error())
+        assert rc in (OK, E_HIP), (N, rc, L.mpcqp_last_error())
+        if rc == OK:
+            L.mpcqp_destroy(ws)
+        else:
+            assert b"hipSetDevice" in L.mpcqp_last_error(), (N, L.mpcqp_last_error())
+
+
 def test_params_key_normalises_bounds_containers():
     """The B=1 controller cache keys bounds by value: tuples, lists, arrays and tuples of arrays of the
     same numbers give one key (one workspace), and none of them is unhashable."""
