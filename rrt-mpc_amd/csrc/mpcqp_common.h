@@ -423,6 +423,25 @@ __device__ __forceinline__ bool class_ok(int c, int K, int b, int32_t* __restric
   return false;
 }
 
+// ------------------------------------------------------------------ the ADMM / polish schedule
+// The ADMM loop state of one QP (admm_run in mpcqp_solve.h, mid_admm in mpcqp_mid.hip).  It lives in the
+// family's driver: the ADMM function stops at a termination check that asks for an early polish and the
+// driver resumes it after a failed attempt, so a kernel holds ONE inlined copy of the polish (attempts,
+// final polish and method newton share the driver's call site) -- the polish is a third of the one-wave
+// kernel's code, which is larger than the 64 KB instruction cache.
+struct AdmmState {
+  double x, z[3], y[3], rho;
+  double rho_next;  // the adaptive-rho update of the check that stopped for an attempt
+  int it, nfact;
+  bool need_fact;   // form + sweep at the next entry (start, rho change, after a failed attempt)
+  bool rho_change;  // rho_next is pending (applied after a failed attempt)
+};
+// What the ADMM function stops for: kAdmmBad (numerical error), kAdmmConverged (eps_abs / eps_rel met),
+// kAdmmAttempt (a check asks for an early polish; rho_change / rho_next hold that check's adaptive-rho
+// decision), kAdmmApprox / kAdmmMaxIter (max_iter reached within / outside 10x the tolerances: OSQP's
+// solved_inaccurate / max_iter_reached).
+enum : int { kAdmmBad = -1, kAdmmMaxIter = 0, kAdmmConverged = 1, kAdmmApprox = 3, kAdmmAttempt = 4 };
+
 }  // namespace
 
 namespace mpcqp {

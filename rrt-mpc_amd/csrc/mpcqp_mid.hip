@@ -1195,19 +1195,12 @@ __device__ __forceinline__ int mid_polish(Mid<NT>& C, double& x, const double zg
 }
 
 // ------------------------------------------------------------------ ADMM (one-wave admm_run)
-struct MidAdmm {
-  double x, z[3], y[3], rho, rho_next;
-  int it, nfact;
-  bool need_fact, rho_change;
-};
-enum : int { kMidBad = -1, kMidMaxIter = 0, kMidConverged = 1, kMidApprox = 3, kMidAttempt = 4 };
-
 template <int NT>
-__device__ __forceinline__ int mid_admm(const mpcqp_params& p, Mid<NT>& C, MidAdmm& S) {
+__device__ __forceinline__ int mid_admm(const mpcqp_params& p, Mid<NT>& C, AdmmState& S) {
   const bool act = C.V && C.act;
   const double sg = p.sigma, alpha = p.alpha;
   const bool early = p.polish != 0 && p.polish_from > 0;
-  int ev = kMidMaxIter;
+  int ev = kAdmmMaxIter;
   bool done = false;
   if (C.V) C.sm->qq[C.i] = C.qv;  // read after the first iteration's barrier
   while (S.it < p.max_iter && !done) {
@@ -1219,7 +1212,7 @@ __device__ __forceinline__ int mid_admm(const mpcqp_params& p, Mid<NT>& C, MidAd
       const bool okf = C.sweep();
       C.T.end(1);
       if (C.bany(!okf)) {
-        ev = kMidBad;
+        ev = kAdmmBad;
         break;
       }
       S.need_fact = false;
@@ -1292,18 +1285,18 @@ __device__ __forceinline__ int mid_admm(const mpcqp_params& p, Mid<NT>& C, MidAd
         const double ed = p.eps_abs + p.eps_rel * ndual * ic;
         C.T.end(3);
         if (nf || !isfinite(pr) || !isfinite(du)) {
-          ev = kMidBad;
+          ev = kAdmmBad;
           done = true;
           break;
         }
         if (pr <= ep && du <= ed) {
-          ev = kMidConverged;
+          ev = kAdmmConverged;
           done = true;
           break;
         }
         if (it == p.max_iter && pr <= 10.0 * p.eps_abs + 10.0 * p.eps_rel * nprim &&
             du <= 10.0 * p.eps_abs + 10.0 * p.eps_rel * ndual * ic)
-          ev = kMidApprox;
+          ev = kAdmmApprox;
         bool rc = false;
         double rn = rho;
         if (p.adaptive_rho && it % p.adaptive_rho_interval == 0) {
@@ -1318,7 +1311,7 @@ __device__ __forceinline__ int mid_admm(const mpcqp_params& p, Mid<NT>& C, MidAd
         if (early && (it >= p.polish_from || near) && it < p.max_iter) {
           S.rho_change = rc;
           S.rho_next = rn;
-          ev = kMidAttempt;
+          ev = kAdmmAttempt;
           done = true;
           break;
         }
@@ -1343,8 +1336,8 @@ __device__ __forceinline__ void mid_finish(const mpcqp_params& p, int b, Mid<NT>
   MidLds<NT>& sm = *C.sm;
   const int N = C.N, n = C.n, i = C.i;
   const bool use_admm = p.method == MPCQP_METHOD_ADMM;
-  const bool approx = admm_flag == kMidApprox;
-  const bool admm_ok = admm_flag == kMidConverged;
+  const bool approx = admm_flag == kAdmmApprox;
+  const bool admm_ok = admm_flag == kAdmmConverged;
   if (C.bany(C.V && C.act && !isfinite(x))) bad = true;
   int status;
   if (bad) {
@@ -1513,7 +1506,7 @@ __global__ __launch_bounds__(MidShape<NT>::kThreads, kMidWaves) void k_solve_mid
   bool bad = mid_setup<NT>(p, C);
   C.T.end(0);
   const bool use_admm = p.method == MPCQP_METHOD_ADMM;
-  MidAdmm A;
+  AdmmState A;
   A.x = 0.0;
 #pragma unroll
   for (int k = 0; k < 3; ++k) A.z[k] = A.y[k] = 0.0;
@@ -1522,22 +1515,24 @@ __global__ __launch_bounds__(MidShape<NT>::kThreads, kMidWaves) void k_solve_mid
   A.nfact = 0;
   A.need_fact = true;
   A.rho_change = false;
-  int flag = bad ? kMidBad : kMidMaxIter, pol_it = 0, n_ls = 0;
+  int flag = bad ? kAdmmBad : kAdmmMaxIter, pol_it = 0, n_ls = 0;
   double x = 0.0, x_admm = 0.0;
   bool do_polish = false, pol_ok = false;
+  // solve_one's schedule (mpcqp_solve.h, commented there) over the mid phases, statement for statement.
+  // Every decision is uniform over the workgroup, so all its threads reach the same barriers.
   while (!bad) {
     int kind = 0;
     double zg[3];
     if (use_admm) {
       const int ev = mid_admm<NT>(p, C, A);
-      if (ev == kMidAttempt) {
+      if (ev == kAdmmAttempt) {
         kind = 1;
       } else {
         flag = ev;
         x = x_admm = C.V && C.act ? A.x : 0.0;
-        do_polish = p.polish != 0 && flag == kMidConverged;
+        do_polish = p.polish != 0 && flag == kAdmmConverged;
         kind = do_polish ? 2 : 0;
-        bad = flag == kMidBad;
+        bad = flag == kAdmmBad;
       }
 #pragma unroll
       for (int k = 0; k < 3; ++k) zg[k] = A.z[k];
@@ -1563,7 +1558,7 @@ __global__ __launch_bounds__(MidShape<NT>::kThreads, kMidWaves) void k_solve_mid
       break;
     }
     if (r_ != 0) {
-      flag = r_ > 0 ? 2 : kMidBad;
+      flag = r_ > 0 ? 2 : kAdmmBad;
       bad = r_ < 0;
       pol_ok = r_ > 0;
       x = x_admm = C.V && C.act ? (pol_ok ? xp : A.x) : 0.0;

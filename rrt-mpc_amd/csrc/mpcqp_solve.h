@@ -1328,23 +1328,8 @@ __device__ __forceinline__ int polish_qp(Ctx<N, Pair>& C, double& x, const doubl
 // OSQP's iteration on the scaled problem (rho / sigma / alpha / adaptive rho / termination as
 // the reference settings).  From iteration polish_from on, a termination check that fails also
 // attempts the polish: an exact optimum found there satisfies the termination test itself.
-// The loop state lives in the caller (AdmmState): admm_run stops at such an attempt and the
-// caller resumes it after a failed one, so the kernel holds ONE inlined copy of the polish (the
-// early attempts, the final polish and method newton share the call site in k_solve) -- the
-// polish is a third of k_solve's code, which is larger than the 64 KB instruction cache.
-struct AdmmState {
-  double x, z[3], y[3], rho;
-  double rho_next;  // the adaptive-rho update of the check that stopped for an attempt
-  int it, nfact;
-  bool need_fact;   // form + sweep at the next entry (start, rho change, after a failed attempt)
-  bool rho_change;  // rho_next is pending (applied after a failed attempt)
-};
-enum : int { kAdmmBad = -1, kAdmmMaxIter = 0, kAdmmConverged = 1, kAdmmApprox = 3, kAdmmAttempt = 4 };
-
-// Runs ADMM until an event: kAdmmBad (numerical error), kAdmmConverged (eps_abs/eps_rel met),
-// kAdmmAttempt (a check asks for an early polish; rho_change/rho_next hold that check's
-// adaptive-rho decision), kAdmmApprox / kAdmmMaxIter (max_iter reached within / outside 10x the
-// tolerances: OSQP's solved_inaccurate / max_iter_reached).
+// admm_run stops at such an attempt with its loop state in the caller's AdmmState (mpcqp_common.h, with
+// the events it returns), and the driver (solve_one, k_solve) polishes and resumes it after a failed one.
 template <int N, bool Pair = false>
 __device__ __forceinline__ int admm_run(const mpcqp_params& p, Ctx<N, Pair>& C, AdmmState& S) {
   using LN = Lanes<Pair>;
@@ -1696,8 +1681,8 @@ __device__ __forceinline__ int finish_qp(const mpcqp_params& p, int b, const dou
 }
 
 // One QP through setup -> ADMM (+ early polish attempts) -> final polish -> outputs on the calling
-// wave, for the fused fleet loop (k_fleet_loop; no debug state): returns the status, Ulane = the
-// lane's U entry (lanes 0 and N: u0).  k_solve runs the same driver inline (below).
+// wave, for k_solve_pair, k_solve_mixed, k_fleet_loop and k_serve (no debug state): returns the status,
+// Ulane = the lane's U entry (lanes 0 and N: u0).  k_solve runs the same driver inline (below).
 template <int N, class Win, bool Pair = false>
 __device__ __forceinline__ int solve_one(const mpcqp_params& p, int b, const double* __restrict__ model,
                                          const double* __restrict__ in_x0, const double* __restrict__ in_ref,
@@ -1819,8 +1804,8 @@ __global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_solve(mpcqp_para
   __shared__ SolveLds<N> sm;
   const int b = blockIdx.x;
   if (b >= B || (mask && !mask[b])) return;
-  // solve_one's driver, kept inline here with the debug state: the headline kernel's code
-  // generation stays independent of the fleet loop's instantiation
+  // solve_one's driver, statement for statement, with the debug state, the stamps and the DIAG switches: as a
+  // call of solve_one the kernel compiles to other code than this, and a lone wave measured 0.6 % slower
   double* dbg = p.debug_state ? state + (size_t)b * state_stride(N) : nullptr;
   const uint64_t t_start = __builtin_amdgcn_s_memtime();
   Stamps TK;

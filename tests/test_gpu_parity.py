@@ -208,6 +208,43 @@ def test_fused_k1_equals_separate_k1(cuda):
         assert np.array_equal(a[k], b[k]), k
 
 
+@pytest.mark.parametrize("N", [3, 20])
+def test_debug_scalars_of_the_solve_driver(cuda, N):
+    """The debug scalars that k_solve's driver writes (debug_state): slot 4 = the wave's cycles,
+    5 / 6 = the polish's factorizations from scratch / rank-1 updates, 7 = its start time.  A polish
+    pass always begins with a factorization from scratch, and the debug state changes no output bit.
+    For one-wave horizons only: from MPCQP_WIDE_MIN_HORIZON on the state slice has the wide layout."""
+    import torch
+    from mpcqp import _lib, scenarios
+    from mpcqp.control.mpc_controller import BatchedMPCController
+
+    B = 8
+    batch = scenarios.config3(B, horizon=N)
+    params = _params(N)
+    plain = _solve(params, batch.x0, batch.ref, batch.u_prev)
+    ctrl = BatchedMPCController(params, B, device="cuda:0", debug_state=1)
+    sol = ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev)
+    torch.cuda.synchronize()
+    out = {k: getattr(sol, k).cpu().numpy().copy() for k in sol._fields}
+    L = _lib.lib()
+    SS = L.mpcqp_state_stride(N)
+    sc = SS - 8  # the eight scalars close a QP's slice
+    if N == 20:
+        assert sc == (4 * 20 * 20 + 7) // 8 * 8 + 15 * 64  # where tools/qp_cycles.py reads them
+    st = _d2h(L.mpcqp_state_buffer(ctrl._ws), np.zeros((B, SS)))
+    ctrl.close()
+    cycles, n_full, n_r1, start = (st[:, sc + k] for k in (4, 5, 6, 7))
+    print(f"N={N}: cycles {cycles}, n_full {n_full}, n_r1 {n_r1}, start {start}, iters {out['iters'].tolist()}")
+    for v in (cycles, start):
+        assert np.isfinite(v).all() and (v > 0).all()
+    for v in (n_full, n_r1):
+        assert np.array_equal(v, np.round(v)) and (v >= 0).all()
+    polished = out["iters"][:, 1] >= 1
+    assert (n_full[polished] >= 1).all()
+    for k in ("u0", "X", "U", "status", "iters", "active"):
+        assert np.array_equal(plain[k], out[k]), k
+
+
 @pytest.mark.parametrize("N", [1, 2, 5, 10, 15, 31])
 def test_horizons(cuda, N):
     from mpcqp import scenarios

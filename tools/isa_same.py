@@ -5,15 +5,17 @@
 
 Takes the compile jobs of ``__graft_entry__._compile_jobs`` of this tree and of OTHER_TREE (a checkout
 of another commit), runs each as ``--cuda-device-only -S`` into a scratch directory, splits the
-assembly into functions, drops comments, replaces the per-file function index of local labels by a
-constant, and compares what is left (instructions, labels, the kernel descriptor) per kernel and
-object.  One line per kernel: ``same``, ``DIFF`` or the tree it is missing from; exit status 1
-on any difference.  Runs on the CPU (cross-compilation only); the order of the kernels in a file and
-the numbering of block labels are not compared.
+assembly into functions, drops comments, numbers the local labels of a function by their first
+appearance in it, and compares what is left (instructions, labels, the kernel descriptor) per kernel
+and object.  One line per kernel: ``same``, ``DIFF`` (with both line counts and the number of differing
+lines) or the tree it is missing from; exit status 1 on any difference.  Runs on the CPU
+(cross-compilation only); the order of the kernels in a file and the compiler's numbering of functions
+and block labels are not compared.
 """
 from __future__ import annotations
 
 import argparse
+import difflib
 import importlib.util
 import re
 import subprocess
@@ -25,7 +27,7 @@ from pathlib import Path
 HERE = Path(__file__).resolve().parents[1]
 BEGIN = re.compile(r"; -- Begin function (\S+)")
 END = re.compile(r"; -- End function")
-LABEL = re.compile(r"\.(LBB|Ltmp|Lfunc_end|Lfunc_begin|LJTI)\d+")
+LABEL = re.compile(r"\.(LBB|Ltmp|Lfunc_end|Lfunc_begin|LJTI)\d+(?:_\d+)*")
 
 
 def _jobs(tree: Path, out: Path) -> dict[str, list[str]]:
@@ -43,16 +45,21 @@ def _jobs(tree: Path, out: Path) -> dict[str, list[str]]:
 
 
 def functions(text: str) -> dict[str, list[str]]:
-    """function name -> its instruction and label lines, comments and local label numbers removed"""
-    out, cur = {}, None
+    """function name -> its instruction and label lines, comments removed and the local labels
+    numbered by first appearance within the function"""
+    out, cur, seen = {}, None, {}
+
+    def number(m):  # `seen` is looked up at each call: the dict of the function being read
+        return seen.setdefault(m.group(0), f".{m.group(1)}#{len(seen)}")
+
     for line in text.splitlines():
         m = BEGIN.search(line)
         if m:
-            cur = out.setdefault(m.group(1), [])
+            cur, seen = out.setdefault(m.group(1), []), {}
         elif END.search(line):
             cur = None
         elif cur is not None:
-            code = LABEL.sub(r".\1#", line.split(";", 1)[0]).strip()
+            code = LABEL.sub(number, line.split(";", 1)[0]).strip()
             if code:
                 cur.append(code)
     return out
@@ -85,7 +92,13 @@ def main() -> int:
                            else "same" if fa[name] == fb[name] else "DIFF")
                 bad += verdict != "same"
                 seen += 1
-                print(f"{obj}: {name}: {verdict} ({len(fa.get(name, fb.get(name)))} lines)")
+                if verdict == "DIFF":
+                    ops = difflib.SequenceMatcher(None, fa[name], fb[name], autojunk=False).get_opcodes()
+                    nd = sum(max(i2 - i1, j2 - j1) for tag, i1, i2, j1, j2 in ops if tag != "equal")
+                    print(f"{obj}: {name}: DIFF (this {len(fa[name])} lines, other {len(fb[name])} lines, "
+                          f"{nd} differ)")
+                else:
+                    print(f"{obj}: {name}: {verdict} ({len(fa.get(name, fb.get(name)))} lines)")
         print(f"{'DIFFERENT' if bad else 'all the same'}: {bad} of {seen} kernels differ or are missing")
         return 1 if bad or not seen else 0
 
