@@ -148,6 +148,24 @@ __device__ __forceinline__ double min_nc(double a, double b) {
 }
 // wave-uniform sum / max: the inclusive scan's last lane
 __device__ __forceinline__ double wave_sum(double v) { return readlane(scan_add(v, 0), 63); }
+// two wave sums at once, each with scan_add's association: the steps alternate, so one sum's DPP moves
+// and their wait states issue under the other's add
+__device__ __forceinline__ void wave_sum2(double& a, double& b) {
+  a += dpp<kRowShr1>(a);
+  b += dpp<kRowShr1>(b);
+  a += dpp<kRowShr2>(a);
+  b += dpp<kRowShr2>(b);
+  a += dpp<kRowShr4>(a);
+  b += dpp<kRowShr4>(b);
+  a += dpp<kRowShr8>(a);
+  b += dpp<kRowShr8>(b);
+  a += dpp_rows<kRowBcast15, 0xa>(a);
+  b += dpp_rows<kRowBcast15, 0xa>(b);
+  a += dpp_rows<kRowBcast31, 0xc>(a);
+  b += dpp_rows<kRowBcast31, 0xc>(b);
+  a = readlane(a, 63);
+  b = readlane(b, 63);
+}
 __device__ __forceinline__ double wave_max(double v) {  // v >= 0
   v = max_nc(v, dpp<kRowShr1>(v));
   v = max_nc(v, dpp<kRowShr2>(v));
@@ -242,6 +260,7 @@ struct Lanes<false> {
   __device__ __forceinline__ static double readv(double v, int l) { return readlane(v, l); }
   __device__ __forceinline__ static int uniform(int l) { return __builtin_amdgcn_readfirstlane(l); }
   __device__ __forceinline__ static double sum(double v) { return wave_sum(v); }
+  __device__ __forceinline__ static void sum2(double& a, double& b) { wave_sum2(a, b); }
   __device__ __forceinline__ static double max(double v) { return wave_max(v); }
   __device__ __forceinline__ static bool any(bool b) { return wave_any(b); }
   __device__ __forceinline__ static uint64_t ballot(bool b) { return __ballot(b); }
@@ -300,6 +319,10 @@ struct Lanes<true> {
     return pin(v);
   }
   __device__ __forceinline__ static double sum(double v) { return read<31>(scan(v, 0)); }
+  __device__ __forceinline__ static void sum2(double& a, double& b) {
+    a = sum(a);
+    b = sum(b);
+  }
   __device__ __forceinline__ static double max(double v) {  // v >= 0
     v = max_nc(v, dpp<kRowShr1>(v));
     v = max_nc(v, dpp<kRowShr2>(v));

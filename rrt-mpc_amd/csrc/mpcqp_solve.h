@@ -414,12 +414,13 @@ struct Ctx {
     const double k2 = lu >= 2 ? LN::readv(tau == 2 ? c22 : 0.0, lu) : 0.0;
     // u = A^{-1} c: c has at most three entries, so u is three columns of the inverse -- by
     // symmetry the lane's own registers r[lu], r[lu-1], r[lu-2] (A^{-1}[i][j] = -r_i[j])
-    double u = k0 * pick<0, n>(lu);
+    // (one descent for the three: pick3)
+    double p0, p1, p2;
+    pick3<0, n>(lu, p0, p1, p2);
     MPCQP_MARK("pol.rank1");
-    if (lu >= 1) u += k1 * pick<0, n>(lu - 1);
-    MPCQP_MARK("pol.rank1");
-    if (lu >= 2) u += k2 * pick<0, n>(lu - 2);
-    MPCQP_MARK("pol.rank1");
+    double u = k0 * p0;
+    if (lu >= 1) u += k1 * p1;
+    if (lu >= 2) u += k2 * p2;
     u = act ? -u : 0.0;
     // u through LDS (the sweep's buffer), as the sweep broadcasts its pivot columns: the three entries
     // of c'u by uniform reads, the rows for the update by the lanes (the pair layout: lane reads and
@@ -450,21 +451,36 @@ struct Ctx {
     });
     return true;
   }
-  // r[j] of this lane for a wave-uniform j: uniform branches down to pairs of registers, one
-  // select in the pair.  The asm pins each pair's value: merged through a phi as one load of a
-  // variable address, the inverse row would be demoted to scratch memory.
+  // r[I] of this lane, 0.0 for an index before the row
+  template <int I>
+  __device__ __forceinline__ double r_or_zero() const {
+    if constexpr (I >= 0) return r[I];
+    else return 0.0;
+  }
+  // r[j], r[j - 1], r[j - 2] of this lane for a wave-uniform j (0.0 where the index is negative): one
+  // descent of uniform branches down to a pair of indices, whose leaf names all three registers
+  // statically (three selects in the pair).  A descent per register, inlined three times per
+  // soft-row slot, was a third of the update's cycles.  The asm pins the leaf's
+  // values: merged through a phi as one load of a variable address, the inverse row would be demoted
+  // to scratch memory.
   template <int LO, int HI>
-  __device__ __forceinline__ double pick(int j) const {
+  __device__ __forceinline__ void pick3(int j, double& v0, double& v1, double& v2) const {
     if constexpr (HI - LO <= 2) {
       MPCQP_MARK("pol.pick_leaf");
-      double v = r[LO];
-      if constexpr (HI - LO == 2) v = j == LO + 1 ? r[LO + 1] : v;
-      asm volatile("" : "+v"(v));
-      return v;
+      v0 = r[LO];
+      v1 = r_or_zero<LO - 1>();
+      v2 = r_or_zero<LO - 2>();
+      if constexpr (HI - LO == 2) {
+        const bool up = j == LO + 1;
+        v0 = up ? r[LO + 1] : v0;
+        v1 = up ? r[LO] : v1;
+        v2 = up ? r_or_zero<LO - 1>() : v2;
+      }
+      asm volatile("" : "+v"(v0), "+v"(v1), "+v"(v2));
     } else {
       constexpr int M = (LO + HI) / 2;
-      if (j < M) return pick<LO, M>(j);
-      return pick<M, HI>(j);
+      if (j < M) pick3<LO, M>(j, v0, v1, v2);
+      else pick3<M, HI>(j, v0, v1, v2);
     }
   }
   // (A^{-1} v)_lane
@@ -1169,7 +1185,12 @@ __device__ __forceinline__ int polish_qp(Ctx<N, Pair>& C, double& x, const doubl
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
       rw[r] = cd[r] ? 2.0 * C.wb[r] : 0.0;
-      tmp[r] = cd[r] == 2 ? rw[r] * C.hi[r] : (cd[r] == 1 ? rw[r] * C.lo[r] : 0.0);
+      // the bound by selects of two registers, one product: written with the products inside the
+      // conditional, each slot compiles to a nest of exec-masked branches
+      const double hi = C.hi[r], lo = C.lo[r];
+      const double bnd = cd[r] == 2 ? hi : lo;
+      const double wbnd = rw[r] * bnd;
+      tmp[r] = cd[r] ? wbnd : 0.0;
     }
     // Factorize the Newton matrix of this active set: from scratch on the first pass, by
     // rank-1 updates of the previous inverse when only a few soft rows changed.
@@ -1272,15 +1293,19 @@ __device__ __forceinline__ int polish_qp(Ctx<N, Pair>& C, double& x, const doubl
     MPCQP_MARK("pol.ls");
     double tb[3];
 #pragma unroll
-    for (int r = 0; r < 3; ++r)
-      tb[r] = rw[r] * (zn[r] - (cd[r] == 2 ? C.hi[r] : (cd[r] == 1 ? C.lo[r] : 0.0)));
+    for (int r = 0; r < 3; ++r) {
+      const double hi = C.hi[r], lo = C.lo[r];
+      const double bnd = cd[r] == 2 ? hi : (cd[r] == 1 ? lo : 0.0);  // selects of registers: no branches
+      tb[r] = rw[r] * (zn[r] - bnd);
+    }
     const double dx = act ? xn - x : 0.0;
     const double Pd = act ? (-C.CTmul(tb) - C.qv) - Px : 0.0;
     double zd[3];
 #pragma unroll
     for (int r = 0; r < 3; ++r) zd[r] = zn[r] - zc[r];
-    const double qd = LN::sum(act ? dx * Pd : 0.0);
-    const double lin = LN::sum(act ? (Px + C.qv) * dx : 0.0);
+    double qd = act ? dx * Pd : 0.0;
+    double lin = act ? (Px + C.qv) * dx : 0.0;
+    LN::sum2(qd, lin);
     double t = 1.0;
     for (int ls = 0; ls < 40; ++ls) {
       MPCQP_MARK("pol.lstrial");
@@ -1295,8 +1320,9 @@ __device__ __forceinline__ int polish_qp(Ctx<N, Pair>& C, double& x, const doubl
         g1 += 2.0 * C.wb[r] * rr * zd[r];
         if (rr != 0.0) g2 += 2.0 * C.wb[r] * zd[r] * zd[r];
       }
-      const double d1 = lin + t * qd + LN::sum(g1);
-      const double d2 = qd + LN::sum(g2);
+      LN::sum2(g1, g2);
+      const double d1 = lin + t * qd + g1;
+      const double d2 = qd + g2;
       if (d1 <= 0.0 || !(d2 > 0.0)) break;
       const double tn = fmax(0.0, t - d1 / d2);
       if (tn >= t) break;
@@ -1306,7 +1332,8 @@ __device__ __forceinline__ int polish_qp(Ctx<N, Pair>& C, double& x, const doubl
       for (int r = 0; r < 3; ++r) {
         // the piece (above / inside / below) changed: lo <= hi, so the two compares decide it
         const double za = zc[r] + t * zd[r], zb = zc[r] + tn * zd[r];
-        moved = moved || ((za > C.hi[r]) != (zb > C.hi[r])) || ((za < C.lo[r]) != (zb < C.lo[r]));
+        // no short circuit: six compares in a row, not a chain of exec-masked branches
+        moved = moved | ((za > C.hi[r]) != (zb > C.hi[r])) | ((za < C.lo[r]) != (zb < C.lo[r]));
       }
       t = tn;
       if (!LN::any(moved)) break;

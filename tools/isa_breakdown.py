@@ -71,9 +71,14 @@ def parse(path: str, kernel: str) -> dict:
     return out
 
 
+def pick3_leaves(lo: int, hi: int) -> int:
+    """Leaves of Ctx::pick3<lo, hi>: it halves the range down to one or two indices."""
+    return 1 if hi - lo <= 2 else pick3_leaves(lo, (lo + hi) // 2) + pick3_leaves((lo + hi) // 2, hi)
+
+
 def weights(work: dict, N: int) -> dict:
     """Executions per QP of each phase, from the kernel's mean work counters.  A rank-1 update reads
-    three columns of the inverse through pick<>'s tree of uniform branches."""
+    three columns of the inverse through one descent of pick3<>'s tree of uniform branches."""
     w = work["work_means"]
     passes = w["polish_pass"]
     return {
@@ -86,9 +91,10 @@ def weights(work: dict, N: int) -> dict:
         "admm.fctl": w["admm_factorization"],
         "admm.iter": w["admm_it"], "admm.check": w["check"],
         # the rank-1 update is inlined once per soft-row slot (3 copies, one runs per update); each
-        # copy reads three inverse columns through pick<>'s uniform branch tree, one leaf of ceil(n/2)
+        # copy reads its three inverse columns in one descent of pick3<>'s uniform branch tree, which
+        # ends in one of the tree's leaves
         "pol.ctl": passes, "pol.rank1": w["rank1_update"] / 3.0,
-        "pol.pick_leaf": w["rank1_update"] / (3.0 * ((2 * N + 1) // 2)),
+        "pol.pick_leaf": w["rank1_update"] / (3.0 * pick3_leaves(0, 2 * N)),
         "pol.form": w["polish_full_factorization"], "pol.sweep": w["polish_full_factorization"],
         "pol.solve": passes, "pol.refine": w["polish_full_factorization"],
         "pol.ls": max(0.0, passes - w["polish_full_factorization"]), "pol.lstrial": w["ls_trial"],

@@ -8,7 +8,15 @@ running after tau cycles is parked (its remaining work + `ovh` cycles of state w
 and resumed after every fresh QP has started.
 
     python tools/tail_sim.py          # host only, ~1 min
+    python tools/tail_sim.py --fit profiles/polish_path/qp_cycles_new.json [--which lone]
+
+With --fit the per-QP model is the one tools/qp_cycles.py wrote (its "fit" of the lone-wave or the
+full batch); without it, the round-2 coefficients.  The C restatement counts neither the polish's
+factorizations from scratch nor its rank-1 updates: the first are spread evenly over the QPs that
+polish (the fit's mean), the second taken in the fit's own mean ratio to the line-search trials.
 """
+import argparse
+import json
 import sys
 from pathlib import Path
 
@@ -19,7 +27,7 @@ sys.path[:0] = [str(ROOT / "rrt-mpc_amd"), str(ROOT / "oracle")]
 CLOCK_CYCLES_PER_US = 2.4e3
 
 
-def qp_costs(B=4096, N=20):
+def qp_costs(B=4096, N=20, fit=None):
     import cpu_solver
     import mpc_oracle as mo
     from mpcqp import scenarios
@@ -28,6 +36,14 @@ def qp_costs(B=4096, N=20):
     out = cpu_solver.cpu_solve(mo.default_params(N), b.x0, b.ref, b.u_prev, nthreads=8)
     it = out["iters"].astype(float)
     checks = np.ceil(it[:, 0] / 25)
+    if fit is not None:
+        c, w = fit["fit"], fit["work_means"]
+        polished = it[:, 1] > 0  # a polish run factorizes from scratch once, whatever its passes
+        full = polished * (w["polish_full_factorization"] / max(polished.mean(), 1e-9))
+        r1 = it[:, 3] * (w["rank1_update"] / w["ls_trial"])
+        return (c["const"] + c["admm_it"] * it[:, 0] + c["check"] * checks
+                + c["admm_factorization"] * (it[:, 2] - it[:, 1]) + c["polish_full_factorization"] * full
+                + c["rank1_update"] * r1 + c["polish_pass"] * it[:, 1] + c["ls_trial"] * it[:, 3])
     return 79334 + 1087 * it[:, 0] + 23912 * it[:, 2] - 19049 * it[:, 1] + 1494 * it[:, 3] + 43 * checks
 
 
@@ -78,7 +94,11 @@ def simulate(cost, order, slots=2048, share=0.82, tau=None, ovh=70000):
 
 
 def main():
-    cost = qp_costs()
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--fit", default=None, help="tools/qp_cycles.py output: use its fitted per-QP model")
+    ap.add_argument("--which", default="lone", choices=("lone", "full"))
+    a = ap.parse_args()
+    cost = qp_costs(fit=json.load(open(a.fit))[a.which] if a.fit else None)
     idx = np.arange(len(cost))
     print(f"per-QP cycles: mean {cost.mean():.0f} max {cost.max():.0f} p99 {np.percentile(cost, 99):.0f}")
     print(f"as generated {simulate(cost, idx):.0f} us; longest-first {simulate(cost, np.argsort(-cost)):.0f} us; "
