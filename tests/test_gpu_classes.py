@@ -8,6 +8,12 @@ controller built with block ``cls[b]`` returns for it: in the one-wave kernel (N
 ignored), the mid kernel (33..64), the wide kernel (N > 64) and reproducible mode.  Classes may differ
 in solver settings and method too (3).  A class index outside the table is reported per QP and never
 indexes anything (4); the calls keep a build tied to the table it was made with (5).
+
+(1) runs at the one-wave horizons only.  The plain controllers that (2) compares with meet the exact
+oracle under every variant on all three kernels: ``test_gpu_params.py`` at N = 10 / 20 / 30 and
+``test_gpu_params_long.py`` at N = 33 / 40 / 49 / 64 (mid) and 65 / 72 (wide), the horizons 33 / 40 /
+64 / 65 of (2) among them -- so a mixed launch at those horizons is tied to the oracle through the
+plain launch it equals bit for bit, not only to itself.
 """
 from __future__ import annotations
 
