@@ -235,6 +235,9 @@ int mpcqp_set_pairing(mpcqp_ws* ws, int mode);
  * mpcqp_set_pairing is ignored for it.  The B = 1 paths (mpcqp_solve_staged, mpcqp_solve_served), the
  * fleet (mpcqp_fleet_*) and the swarm (mpcqp_swarm_*) keep using the workspace's own block, whatever
  * table it holds.
+ *
+ * The one fleet call that reads the tables is mpcqp_fleet_loop_mixed (below, after mpcqp_fleet_loop): the
+ * fused closed loop with a class per vehicle.  Fused loop only, never paired; the swarm is unchanged.
  */
 #define MPCQP_BAD_CLASS (-11)   /* per-QP status: class index outside [0, K) */
 
@@ -317,6 +320,28 @@ int mpcqp_fleet_run(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, 
  * other parameter blocks (mid / long horizons, reproducible or debug_state) are executed by
  * mpcqp_fleet_run's graph path. */
 int mpcqp_fleet_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, int steps, void* stream);
+
+/* mpcqp_fleet_loop for a heterogeneous fleet (additive to ABI 9): vehicle v solves its nominal QP under
+ * block cls[v] of `nominal`'s class table and retries under block cls[v] of `relaxed`'s table
+ * (mpcqp_set_classes on both, the same K >= 1; MPCQP_E_STATE otherwise, the message names the
+ * workspace); its plant uses dt and wheelbase_px of its nominal block.  cls: V int32 in device memory,
+ * valid until the launch has run (stream order); NULL -> MPCQP_E_ARG.  Vehicle v's buffers are, bit for
+ * bit, those of mpcqp_fleet_loop for a homogeneous fleet under its class's two blocks.  Argument checks,
+ * the device's validation of the loop state, the goal / abort / out-of-steps exits, the longest-first
+ * dispatch and the invalidation of both workspaces' builds are mpcqp_fleet_loop's.
+ * A RUNNING vehicle whose cls[v] lies outside [0, K) never indexes a table: its phase becomes
+ * MPCQP_FLEET_ABORTED, status[v] MPCQP_BAD_CLASS, mask[v] and mask[V + v] 0, and nothing else of it is
+ * written; the other vehicles run as usual.  A vehicle that is not RUNNING is skipped before its class
+ * is read.
+ * Limits: the fused loop only -- N <= 32 in fast mode without debug_state; other parameter blocks
+ * return MPCQP_E_HORIZON, and then nothing is enqueued and nothing invalidated.  Never paired: a mixed
+ * loop runs one vehicle per wave whatever mpcqp_set_pairing says (two vehicles of different classes per
+ * wave would need two blocks).  The replan trigger is off and the swarm is unchanged (its replanning
+ * builds references with one dt).  Out of scope: mixed mpcqp_fleet_step / mpcqp_fleet_run (and with
+ * them horizons above 32, reproducible mode and debug_state: the stepped path would need a mask and a
+ * model input in the three mixed solve kernels), the swarm, and the B = 1 paths. */
+int mpcqp_fleet_loop_mixed(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const int32_t* cls, int steps,
+                           void* stream);
 
 /*
  * Batched build_reference: src/control/ref_builder.py:10-22 with

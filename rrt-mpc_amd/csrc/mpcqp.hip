@@ -217,6 +217,10 @@ fleet_loop_t fleet_looper(const mpcqp_params& p) {
   const HorizonKernels* k = one_wave(p, false);
   return k ? k->loop : nullptr;
 }
+fleet_loop_mixed_t fleet_looper_mixed(const mpcqp_params& p) {
+  const HorizonKernels* k = one_wave(p, false);
+  return k ? k->loop_mixed : nullptr;
+}
 }  // namespace mpcqp
 
 extern "C" {
@@ -331,6 +335,7 @@ void mpcqp_destroy(mpcqp_ws* ws) {
   (void)hipFree(ws->dparams);
   (void)hipFree(ws->dorder);
   (void)hipFree(ws->dclasses);
+  (void)hipFree(ws->dloop_classes);
   if (ws->serve_box) (void)hipHostFree(ws->serve_box);
   if (ws->stage_in) (void)hipHostFree(ws->stage_in);
   if (ws->stage_out) (void)hipHostFree(ws->stage_out);

@@ -527,21 +527,28 @@ typedef void (*serve_t)(hipStream_t, const mpcqp_params&, const ServeLaunch&);
 // nullptr when the parameter block does not run the one-wave kernel; defined in mpcqp.hip
 serve_t server(const mpcqp_params& p);
 typedef void (*fleet_loop_t)(hipStream_t, const mpcqp_params*, const mpcqp_fleet&, int, const LoopTrigger&);
+// the fused loop with a class per vehicle: the table of 2K interleaved blocks, cls (V indices), K, the
+// fleet, steps, the dispatch order (or nullptr)
+typedef void (*fleet_loop_mixed_t)(hipStream_t, const mpcqp_params*, const int32_t*, int, const mpcqp_fleet&, int,
+                                   const int32_t*);
 // The kernels of one horizon of the one-wave family (N < MPCQP_WIDE_MIN_HORIZON; the launch_*<N>
 // templates of mpcqp_solve.h): k_solve, k_solve_mixed (a parameter block per QP), k_solve_pair (two
-// QPs per wave, fused K1; nullptr above kPairMaxHorizon), k_serve (the B = 1 server) and k_fleet_loop
-// (the fused closed loop).  The object that instantiates a horizon registers it from a namespace-scope
+// QPs per wave, fused K1; nullptr above kPairMaxHorizon), k_serve (the B = 1 server), k_fleet_loop
+// (the fused closed loop) and k_fleet_loop_mixed (the same with a class per vehicle).  The object that
+// instantiates a horizon registers it from a namespace-scope
 // initialiser (register_horizons, mpcqp_solve.h); an all-null entry is a horizon not compiled in.
 struct HorizonKernels {
   launcher_t solve, mixed, pair;
   serve_t serve;
   fleet_loop_t loop;
+  fleet_loop_mixed_t loop_mixed;
 };
 // fills entry N of the table in mpcqp.hip (constant-initialised, so the order of the objects'
 // initialisers does not matter)
 void register_horizon(int N, const HorizonKernels& k);
 // nullptr when the parameter block does not run the one-wave kernel; defined in mpcqp.hip
 fleet_loop_t fleet_looper(const mpcqp_params& p);
+fleet_loop_mixed_t fleet_looper_mixed(const mpcqp_params& p);
 // k_solve_pair / k_fleet_loop<N, true> for `count` QPs or vehicles of this workspace's launch?
 bool use_pairs(const mpcqp_ws* ws, int count);
 // the long-horizon solve (N >= MPCQP_WIDE_MIN_HORIZON; mpcqp_wide.hip): one 256-thread workgroup
@@ -645,6 +652,10 @@ struct mpcqp_ws {
   // per-QP parameter classes (mpcqp_set_classes): the device table of n_classes blocks
   mpcqp_params* dclasses = nullptr;
   int n_classes = 0;
+  // mpcqp_fleet_loop_mixed (on the nominal workspace): 2 K blocks {nominal[c], relaxed[c]} for
+  // dloop_cap classes, filled from the two class tables by a kernel on the launch stream at every call
+  mpcqp_params* dloop_classes = nullptr;
+  int dloop_cap = 0;
 };
 
 namespace mpcqp {

@@ -123,6 +123,20 @@ __global__ __launch_bounds__(kWave) void k_store_params(mpcqp_params pn, mpcqp_p
   }
 }
 
+// the 2 K blocks of one mpcqp_fleet_loop_mixed call, T = {nominal[0], relaxed[0], nominal[1], ...}, from
+// the two workspaces' class tables (workgroup c copies class c), stream-ordered before the loop kernel
+__global__ __launch_bounds__(kWave) void k_store_classes(const mpcqp_params* __restrict__ nom,
+                                                         const mpcqp_params* __restrict__ rel, int K,
+                                                         mpcqp_params* __restrict__ T) {
+  constexpr int W = (int)(sizeof(mpcqp_params) / 4);
+  const int c = blockIdx.x;
+  if (c >= K) return;
+  for (int w = threadIdx.x; w < W; w += kWave) {
+    reinterpret_cast<uint32_t*>(T + 2 * (size_t)c)[w] = reinterpret_cast<const uint32_t*>(nom + c)[w];
+    reinterpret_cast<uint32_t*>(T + 2 * (size_t)c + 1)[w] = reinterpret_cast<const uint32_t*>(rel + c)[w];
+  }
+}
+
 // The fused loop's dispatch order: the vehicles by reference length, longest first (a bucket sort
 // on the length, 1024 buckets; the order inside a bucket is immaterial -- vehicles are independent).
 // One 1024-thread workgroup.
@@ -291,6 +305,54 @@ int mpcqp_fleet_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f,
   rc = mpcqp::enqueue_fleet_loop(nominal, relaxed, f, steps, mpcqp::LoopTrigger{0.0, 0, nullptr, nullptr}, s, &fused);
   if (rc || fused) return rc;
   return run_graph(nominal, relaxed, f, steps, s);  // mid / long horizons, reproducible or debug mode
+}
+
+int mpcqp_fleet_loop_mixed(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const int32_t* cls, int steps,
+                           void* stream) {
+  if (!cls) return fail(MPCQP_E_ARG, "null cls");
+  int rc = check_fleet(nominal, relaxed, f);
+  if (rc) return rc;
+  if (steps < 0) return fail(MPCQP_E_ARG, "steps must be >= 0");
+  // the fused one-wave kernel only; refused before anything is enqueued or invalidated
+  const mpcqp::fleet_loop_mixed_t loop = mpcqp::fleet_looper_mixed(nominal->p);
+  if (!loop || mpcqp::fleet_looper_mixed(relaxed->p) != loop)
+    return fail(MPCQP_E_HORIZON, "mpcqp_fleet_loop_mixed runs the fused one-wave loop only (N <= 32, fast mode, no "
+                                 "debug_state): the stepped fleet has no per-vehicle classes");
+  const int K = nominal->n_classes;
+  if (K < 1 || !nominal->dclasses)
+    return fail(MPCQP_E_STATE, "mpcqp_fleet_loop_mixed: the nominal workspace holds no class table (mpcqp_set_classes)");
+  if (relaxed->n_classes < 1 || !relaxed->dclasses)
+    return fail(MPCQP_E_STATE, "mpcqp_fleet_loop_mixed: the relaxed workspace holds no class table (mpcqp_set_classes)");
+  if (relaxed->n_classes != K)
+    return fail(MPCQP_E_STATE, "mpcqp_fleet_loop_mixed: the relaxed workspace holds " + std::to_string(relaxed->n_classes) +
+                                   " classes, the nominal workspace " + std::to_string(K));
+  if (f->vehicles == 0 || steps == 0) return MPCQP_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (nominal->dloop_cap < K) {  // the interleaved table grows outside any capture (hipFree waits for its readers)
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (s && hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+      return fail(MPCQP_E_STATE, "the mixed loop's class table is allocated at its first use, which cannot be inside "
+                                 "a stream capture: run the call once uncaptured first");
+    const mpcqp::DeviceGuard dev(nominal->device);
+    hipError_t e = dev.err;
+    mpcqp_params* table = nullptr;
+    if (e == hipSuccess) e = hipMalloc(&table, 2 * sizeof(mpcqp_params) * (size_t)K);
+    if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("hipMalloc (mixed loop classes): ") + hipGetErrorString(e));
+    if (nominal->dloop_classes) (void)hipFree(nominal->dloop_classes);
+    nominal->dloop_classes = table;
+    nominal->dloop_cap = K;
+  }
+  nominal->invalidate();  // as mpcqp_fleet_loop: a later mpcqp_solve needs its own build
+  relaxed->invalidate();
+  hipLaunchKernelGGL(k_store_classes, dim3(K), dim3(kWave), 0, s, nominal->dclasses, relaxed->dclasses, K,
+                     nominal->dloop_classes);
+  const int32_t* order = nullptr;
+  if (nominal->cus > 0 && f->vehicles > 8 * nominal->cus) {  // longest first, as mpcqp_fleet_loop
+    hipLaunchKernelGGL(k_fleet_order, dim3(1), dim3(kOrderBuckets), 0, s, *f, nominal->dorder);
+    order = nominal->dorder;
+  }
+  loop(s, nominal->dloop_classes, cls, K, *f, steps, order);
+  return mpcqp::launched("k_fleet_loop_mixed");
 }
 
 int mpcqp_fleet_run(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, int steps, int use_graph,

@@ -2000,22 +2000,16 @@ __global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_solve_mixed(cons
 // in LDS across steps (no registers held through the solve); it is written back at the end.
 // Pair: two vehicles per wave (N <= 15; lanes 0-31 / 32-63, as k_solve_pair), each half its own
 // loop state, LDS block and control flow.
-template <int N, bool Pair = false>
-__global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_fleet_loop(const mpcqp_params* __restrict__ P,
-                                                                         mpcqp_fleet f, int steps,
-                                                                         mpcqp::LoopTrigger tr) {
+//
+// fleet_loop_body: the loop of one vehicle b (< V) on its wave or half-wave, shared by k_fleet_loop and
+// k_fleet_loop_mixed (which hands in P offset to the vehicle's pair of blocks).  ls: the vehicle's six
+// doubles of loop state in LDS, sm its solver LDS.
+template <int N, bool Pair>
+__device__ __forceinline__ void fleet_loop_body(const mpcqp_params* __restrict__ P, const mpcqp_fleet& f, int steps,
+                                                const mpcqp::LoopTrigger& tr, int b, int lane,
+                                                SolveLds<N, Pair>& sm, double* const ls) {
   using LN = Lanes<Pair>;
-  __shared__ SolveLds<N, Pair> smv[Pair ? 2 : 1];
-  __shared__ double lsv[Pair ? 12 : 6];  // loop state: x[4], u_prev[2] (per half)
-  const int h = Pair ? (int)(threadIdx.x >> 5) : 0;
-  SolveLds<N, Pair>& sm = smv[h];
-  double* const ls = lsv + 6 * h;
-  const int slot = 2 * (int)blockIdx.x + h;  // pair: may be V (odd V)
-  const int b = Pair ? ((tr.order && slot < f.vehicles) ? tr.order[slot] : slot)
-                     : (tr.order ? tr.order[blockIdx.x] : (int)blockIdx.x);
-  const int lane = Pair ? (int)(threadIdx.x & 31) : (int)threadIdx.x;
   const int V = f.vehicles;
-  if (b >= V) return;
   int phase = f.phase[b];
   // the swarm's trigger (mpcqp_swarm_loop): replans left for this vehicle
   const bool can_replan = tr.max_replans > 0 && tr.replans[b] >= 0 && tr.replans[b] < tr.max_replans;
@@ -2126,6 +2120,59 @@ __global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_fleet_loop(const
   }
 }
 
+template <int N, bool Pair = false>
+__global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_fleet_loop(const mpcqp_params* __restrict__ P,
+                                                                         mpcqp_fleet f, int steps,
+                                                                         mpcqp::LoopTrigger tr) {
+  __shared__ SolveLds<N, Pair> smv[Pair ? 2 : 1];
+  __shared__ double lsv[Pair ? 12 : 6];  // loop state: x[4], u_prev[2] (per half)
+  const int h = Pair ? (int)(threadIdx.x >> 5) : 0;
+  SolveLds<N, Pair>& sm = smv[h];
+  double* const ls = lsv + 6 * h;
+  const int slot = 2 * (int)blockIdx.x + h;  // pair: may be V (odd V)
+  const int b = Pair ? ((tr.order && slot < f.vehicles) ? tr.order[slot] : slot)
+                     : (tr.order ? tr.order[blockIdx.x] : (int)blockIdx.x);
+  const int lane = Pair ? (int)(threadIdx.x & 31) : (int)threadIdx.x;
+  const int V = f.vehicles;
+  if (b >= V) return;
+  fleet_loop_body<N, Pair>(P, f, steps, tr, b, lane, sm, ls);
+}
+
+// ------------------------------------------------------------------ fused closed loop, a class per vehicle
+// mpcqp_fleet_loop_mixed: vehicle b runs k_fleet_loop's body under the blocks of its class c = cls[b],
+// P = {nominal[0], relaxed[0], nominal[1], relaxed[1], ...} (2K blocks in global memory): the nominal
+// solve under P[2c], the retry under P[2c + 1], the plant with P[2c]'s dt and wheelbase.  c is uniform
+// over the wave, so the offset is one scalar add before the step loop, and the body's own P[relax]
+// stays what it is: the vehicle's buffers are those of k_fleet_loop<N> under its class's blocks, bit
+// for bit.  One vehicle per wave, no replan trigger.  A vehicle that is not RUNNING is skipped before
+// its class is read; a RUNNING one whose index lies outside [0, K) never indexes the table: it is
+// ABORTED with status MPCQP_BAD_CLASS and both masks 0, and nothing else of it is written.
+template <int N>
+__global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_fleet_loop_mixed(const mpcqp_params* __restrict__ P,
+                                                                               const int32_t* __restrict__ cls, int K,
+                                                                               mpcqp_fleet f, int steps,
+                                                                               const int32_t* __restrict__ order) {
+  __shared__ SolveLds<N> sm;
+  __shared__ double ls[6];  // loop state: x[4], u_prev[2]
+  const int b = order ? order[blockIdx.x] : (int)blockIdx.x;
+  const int lane = (int)threadIdx.x;
+  const int V = f.vehicles;
+  if (b < 0 || b >= V) return;
+  if (f.phase[b] != MPCQP_FLEET_RUNNING) return;
+  const int c = cls[b];
+  if ((unsigned)c >= (unsigned)K) {
+    if (lane == 0) {
+      f.phase[b] = MPCQP_FLEET_ABORTED;
+      f.status[b] = MPCQP_BAD_CLASS;
+      f.mask[b] = 0;
+      f.mask[(size_t)V + b] = 0;
+    }
+    return;
+  }
+  const mpcqp::LoopTrigger off{0.0, 0, nullptr, nullptr};
+  fleet_loop_body<N, false>(P + 2 * (size_t)c, f, steps, off, b, lane, sm, ls);
+}
+
 // ------------------------------------------------------------------ B = 1 server
 // One resident wave serving the sequential closed loop of TrajectoryTracker.track: it waits for the
 // host to raise box->req (system-scope loads of pinned host memory, s_sleep between polls), solves the
@@ -2195,6 +2242,11 @@ void launch_fleet_loop(hipStream_t s, const mpcqp_params* P, const mpcqp_fleet& 
   }
   hipLaunchKernelGGL(k_fleet_loop<N>, dim3(f.vehicles), dim3(kWave), 0, s, P, f, steps, tr);
 }
+template <int N>
+void launch_fleet_loop_mixed(hipStream_t s, const mpcqp_params* P, const int32_t* cls, int K, const mpcqp_fleet& f,
+                             int steps, const int32_t* order) {
+  hipLaunchKernelGGL(k_fleet_loop_mixed<N>, dim3(f.vehicles), dim3(kWave), 0, s, P, cls, K, f, steps, order);
+}
 // two QPs per wave (N <= kPairMaxHorizon, fused K1, no debug state)
 template <int N>
 void launch_solve_pair(hipStream_t s, const Launch& L) {
@@ -2208,7 +2260,8 @@ void launch_solve_pair(hipStream_t s, const Launch& L) {
 // instantiates the kernels).  A new per-horizon entry point: a member of HorizonKernels, and here.
 template <int LO, int HI>
 int register_horizons() {
-  HorizonKernels k{&launch_solve<LO>, &launch_solve_mixed<LO>, nullptr, &launch_serve<LO>, &launch_fleet_loop<LO>};
+  HorizonKernels k{&launch_solve<LO>, &launch_solve_mixed<LO>, nullptr, &launch_serve<LO>, &launch_fleet_loop<LO>,
+                   &launch_fleet_loop_mixed<LO>};
   if constexpr (LO <= kPairMaxHorizon) k.pair = &launch_solve_pair<LO>;
   register_horizon(LO, k);
   if constexpr (LO < HI) return register_horizons<LO + 1, HI>();

@@ -285,6 +285,8 @@ _SYMBOLS = {
                          ctypes.c_void_p], ctypes.c_int),
     "mpcqp_fleet_loop": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MpcqpFleet), ctypes.c_int,
                           ctypes.c_void_p], ctypes.c_int),
+    "mpcqp_fleet_loop_mixed": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MpcqpFleet), ctypes.c_void_p,
+                                ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
     "mpcqp_build_reference": ([ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double,
                                ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                ctypes.c_void_p], ctypes.c_int),

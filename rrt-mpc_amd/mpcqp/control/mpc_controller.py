@@ -99,6 +99,28 @@ def _params_key(params, method: int, settings: dict) -> tuple:
     )
 
 
+def class_input(torch, device, classes, B):
+    """Class indices (int array or integer tensor) as an int32 tensor of shape (B,) on ``device``; a
+    tensor of that type and place is used as it is.  Shared by ``solve_batch(classes=...)`` and
+    ``FleetTracker``."""
+    if isinstance(classes, torch.Tensor):
+        if classes.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+            raise ValueError(f"classes must be an integer tensor, got {classes.dtype}")
+        t = classes
+    else:
+        a = np.asarray(classes)
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"classes must be an integer array, got dtype {a.dtype}")
+        # values outside int32 are no class indices: kept out of range (the device reports them per QP)
+        a = np.where((a < 0) | (a > 2**31 - 1), -1, a).astype(np.int32)
+        t = torch.from_numpy(np.ascontiguousarray(a))
+    if tuple(t.shape) != (B,):
+        raise ValueError(f"classes must have shape ({B},), got {tuple(t.shape)}")
+    if t.device != device or t.dtype != torch.int32:
+        t = t.to(device=device, dtype=torch.int32)
+    return t.contiguous()
+
+
 class BatchedMPCController:
     """Solve B independent MPC QPs per call on one GPU.
 
@@ -192,23 +214,7 @@ class BatchedMPCController:
 
     def _class_input(self, classes, B):
         """``classes`` as an int32 device tensor of shape (B,) (a device tensor of that type is used in place)."""
-        torch = self._torch
-        if isinstance(classes, torch.Tensor):
-            if classes.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
-                raise ValueError(f"classes must be an integer tensor, got {classes.dtype}")
-            t = classes
-        else:
-            a = np.asarray(classes)
-            if a.dtype.kind not in "iu":
-                raise ValueError(f"classes must be an integer array, got dtype {a.dtype}")
-            # values outside int32 are no class indices: kept out of range (the device reports them per QP)
-            a = np.where((a < 0) | (a > 2**31 - 1), -1, a).astype(np.int32)
-            t = torch.from_numpy(np.ascontiguousarray(a))
-        if tuple(t.shape) != (B,):
-            raise ValueError(f"classes must have shape ({B},), got {tuple(t.shape)}")
-        if t.device != self.device or t.dtype != torch.int32:
-            t = t.to(device=self.device, dtype=torch.int32)
-        return t.contiguous()
+        return class_input(self._torch, self.device, classes, B)
 
     def _device_input(self, a, shape, name):
         torch = self._torch

@@ -11,6 +11,11 @@ device.  The host only checks every ``check_every`` steps whether any vehicle st
 no kernel boundary per step, and leaves the loop at its goal -- the same operations, so the
 traces are bit-identical to the stepped path.
 
+A heterogeneous fleet (several wheelbases, limits, weights or a per-vehicle ``dt``) runs in the same
+single launch: ``set_classes([params_0, ...])`` loads K parameter blocks and ``reset(..., classes=cls)``
+gives vehicle ``v`` block ``cls[v]`` (``mpcqp_fleet_loop_mixed``, fused loop only); its buffers equal a
+homogeneous fused fleet's under that block bit for bit.
+
 Each vehicle follows exactly the reference's single-vehicle semantics, so vehicle ``v``
 reproduces ``TrajectoryTracker.track`` on its own plan (tests/test_gpu_fleet.py).
 """
@@ -102,19 +107,22 @@ class FleetTracker:
     """V vehicles in closed loop on one GPU; every loop step runs on the device.
 
     ``mpc`` is an ``MPCConfig`` (reference or ``mpcqp.config``); the solver parameters
-    are ``mpc.to_parameters(map_resolution)`` as in ``control_stage.py:73``.
+    are ``mpc.to_parameters(map_resolution)`` as in ``control_stage.py:73``, or ``params`` (an
+    ``MPCParameters`` of the same horizon) where given: blocks an ``MPCConfig`` cannot express, such as
+    a non-diagonal Q.
     """
 
     def __init__(self, mpc, *, map_resolution: float, max_vehicles: int, max_ref_len: int,
                  device=None, use_graph: bool = True, fused: bool = False,
-                 relaxed_settings: Optional[dict] = None, **settings) -> None:
+                 relaxed_settings: Optional[dict] = None, params=None, **settings) -> None:
         import torch
 
         from ..control.mpc_controller import BatchedMPCController
 
         self._torch = torch
         self.mpc = mpc
-        self.params = mpc.to_parameters(map_resolution)
+        self.params = mpc.to_parameters(map_resolution) if params is None else params
+        self._ref_dt = float(mpc.dt if params is None else params.dt)  # reset_from_plans builds references with it
         self.horizon = int(self.params.horizon)
         self.max_vehicles = int(max_vehicles)
         self.max_ref_len = int(max_ref_len)
@@ -135,14 +143,67 @@ class FleetTracker:
         self._bufs = None
         self._fleet = None
         self.vehicles = 0
+        self.num_classes = 0
+        self._class_params = None
+
+    # ------------------------------------------------------------------
+    def set_classes(self, params_list, settings=None, relaxed_settings=None) -> None:
+        """Per-vehicle parameter classes for the fused loop: block k of the nominal controller is
+        ``params_list[k]``, block k of the retry ``relaxed_parameters(params_list[k])`` (both through
+        ``BatchedMPCController.set_classes``: ``settings`` / ``relaxed_settings`` are one dict for all
+        classes or a list with one per class, on top of the controller's own; the retry's default to
+        the nominal ones, as in the constructor).  ``reset(..., classes=cls)`` then gives vehicle v
+        block ``cls[v]`` (class 0 without ``classes``), and ``step`` / ``run`` call
+        ``mpcqp_fleet_loop_mixed``.  ``None`` or ``[]`` drops the tables: the tracker is homogeneous
+        again.  Needs ``fused=True`` and a horizon of at most 32 (the stepped loop has no classes)."""
+        if not params_list:
+            self._nominal.set_classes(None)
+            self._relaxed.set_classes(None)
+            self.num_classes = 0
+            self._class_params = None
+            return
+        if not self.fused:
+            raise ValueError("set_classes needs fused=True: only the fused loop runs per-vehicle classes")
+        if self.horizon > 32:
+            raise ValueError(f"set_classes needs a horizon <= 32 (the fused loop), got {self.horizon}")
+        params_list = list(params_list)
+        self._nominal.set_classes(params_list, settings)
+        self._relaxed.set_classes([relaxed_parameters(p) for p in params_list],
+                                  settings if relaxed_settings is None else relaxed_settings)
+        self.num_classes = len(params_list)
+        self._class_params = params_list
+
+    def _class_indices(self, classes, V: int):
+        """``classes`` as the int32 device tensor ``mpcqp_fleet_loop_mixed`` reads (None without a table)."""
+        from ..control.mpc_controller import class_input
+
+        if classes is None:
+            if not self.num_classes:
+                return None
+            return self._torch.zeros((max(V, 1),), dtype=self._torch.int32, device=self.device)
+        if not self.num_classes:
+            raise ValueError("classes=... needs a class table: call set_classes first")
+        t = class_input(self._torch, self.device, classes, V)
+        return t if V else self._torch.zeros((1,), dtype=self._torch.int32, device=self.device)
+
+    def _class_dts(self, cls, V: int) -> np.ndarray:
+        """dt of each vehicle's class (the tracker's own where the index is out of range: that
+        vehicle is aborted before it reads its reference)."""
+        dts = np.array([float(p.dt) for p in self._class_params])
+        c = cls[:V].cpu().numpy().astype(np.int64)
+        ok = (c >= 0) & (c < len(dts))
+        return np.where(ok, dts[np.where(ok, c, 0)], float(self.params.dt))
 
     # ------------------------------------------------------------------
     def reset(self, ref_globals: Sequence[np.ndarray], states0: np.ndarray, goals: np.ndarray,
-              max_steps: Optional[int] = None) -> None:
-        """Load V references (each ``(M_v, 4)``, ``build_reference`` output), start states and goals."""
+              max_steps: Optional[int] = None, *, classes=None) -> None:
+        """Load V references (each ``(M_v, 4)``, ``build_reference`` output), start states and goals.
+        ``classes`` (int array or int32 device tensor, shape ``(V,)``): vehicle v's block of
+        ``set_classes``; an index outside the table aborts that vehicle with status ``BAD_CLASS``."""
         V = len(ref_globals)
         if V > self.max_vehicles:
             raise ValueError(f"{V} vehicles exceed max_vehicles {self.max_vehicles}")
+        cls = self._class_indices(classes, V)
         states0 = np.asarray(states0, dtype=float).reshape(V, 4)
         goals = np.asarray(goals, dtype=float).reshape(V, 2)
         max_steps = int(self.mpc.sim_steps if max_steps is None else max_steps)
@@ -158,10 +219,10 @@ class FleetTracker:
             if r.ndim != 2 or r.shape[1] != 4:
                 raise ValueError("each reference must have shape (M, 4)")
             ref[v, : len(r)] = r
-        self._load(V, ref, lens, states0, goals, max_steps)
+        self._load(V, ref, lens, states0, goals, max_steps, cls)
 
     def _load(self, V: int, ref: Optional[np.ndarray], lens: np.ndarray, states0: np.ndarray, goals: np.ndarray,
-              max_steps: Optional[int]) -> None:
+              max_steps: Optional[int], cls=None) -> None:
         """The fleet's device buffers for V vehicles; ``ref`` None: the references are copied in on the
         device afterwards (reset_device), so no host copy of them is built or uploaded."""
         torch = self._torch
@@ -198,44 +259,56 @@ class FleetTracker:
         f.max_steps = max_steps
         for name, t in b.items():
             setattr(f, name, t.data_ptr())
+        # the vehicles' class indices (mpcqp_fleet_loop_mixed's argument, not a member of mpcqp_fleet)
+        b["cls"] = cls if cls is not None else torch.zeros((max(V, 1),), dtype=i32, **dev)
         self._bufs = b
         self._fleet = f
         self.vehicles = V
         self.max_steps = max_steps
 
     def reset_from_plans(self, paths: Sequence, starts: np.ndarray, goals: np.ndarray,
-                         max_steps: Optional[int] = None, *, device_reference: bool = False):
+                         max_steps: Optional[int] = None, *, device_reference: bool = False, classes=None):
         """``control_stage.py:69-87`` per vehicle: references from the planned paths, start states.
+        With ``classes`` vehicle v's reference is built with its class's ``dt`` (host path; the batched
+        device builder takes one ``dt``, so ``device_reference=True`` needs classes that share it).
 
         ``device_reference=True`` builds the references with the batched GPU ``build_reference``
         (``mpcqp_build_reference``) straight into the fleet's buffers; otherwise on the host.
         Returns the host references (or ``(ref, ref_len)`` device tensors)."""
+        V = len(paths)
+        cls = self._class_indices(classes, V)
+        cls = None if cls is None else cls[:V]
+        dts = np.full(V, self._ref_dt) if cls is None else self._class_dts(cls, V)
+        if device_reference and cls is not None and len(set(float(p.dt) for p in self._class_params)) > 1:
+            raise ValueError("device_reference=True builds every reference with one dt, the classes have several: "
+                             "build the references on the host (device_reference=False)")
         packed = PackedPaths(paths)
         states0 = initial_states(paths, starts, packed)
         if device_reference:
-            ref, ref_len = build_reference_batch(paths, self.mpc.v_px_s, self.horizon, self.mpc.dt,
+            ref, ref_len = build_reference_batch(paths, self.mpc.v_px_s, self.horizon, float(dts[0]) if V else self._ref_dt,
                                                  device=self.device, ref_stride=self.max_ref_len, packed=packed)
-            self.reset_device(ref, ref_len, states0, goals, max_steps)
+            self.reset_device(ref, ref_len, states0, goals, max_steps, classes=cls)
             return ref, ref_len
-        refs = [build_reference(path, self.mpc.v_px_s, self.horizon, self.mpc.dt) for path in paths]
-        self.reset(refs, states0, goals, max_steps)
+        refs = [build_reference(path, self.mpc.v_px_s, self.horizon, float(dts[v])) for v, path in enumerate(paths)]
+        self.reset(refs, states0, goals, max_steps, classes=cls)
         return refs
 
     def reset_device(self, ref, ref_len, states0: np.ndarray, goals: np.ndarray,
-                     max_steps: Optional[int] = None) -> None:
+                     max_steps: Optional[int] = None, *, classes=None) -> None:
         """Load references already on the device: ``ref`` (V, max_ref_len, 4) float64 and
-        ``ref_len`` (V,) int32 as produced by ``build_reference_batch``."""
+        ``ref_len`` (V,) int32 as produced by ``build_reference_batch``.  ``classes``: as ``reset``."""
         torch = self._torch
         V = int(ref.shape[0])
         if V > self.max_vehicles:
             raise ValueError(f"{V} vehicles exceed max_vehicles {self.max_vehicles}")
+        cls = self._class_indices(classes, V)
         if int(ref.shape[1]) != self.max_ref_len:
             raise ValueError(f"ref rows {int(ref.shape[1])} != max_ref_len {self.max_ref_len}")
         lens = ref_len.cpu().numpy()
         if V and (lens.min() < 1 or lens.max() > self.max_ref_len):
             raise ValueError(f"reference lengths must be in [1, {self.max_ref_len}] (build_reference_batch "
                              f"reports overflow as negative lengths)")
-        self._load(V, None, lens.astype(np.int32), states0, goals, max_steps)
+        self._load(V, None, lens.astype(np.int32), states0, goals, max_steps, cls)
         self._bufs["ref_global"][:V].copy_(ref)
         self._bufs["ref_len"][:V].copy_(ref_len.to(torch.int32))
 
@@ -248,6 +321,11 @@ class FleetTracker:
         if stream is None:
             stream = torch.cuda.current_stream(self.device)
         s = ctypes.c_void_p(stream.cuda_stream)
+        if self.num_classes:  # a class per vehicle (set_classes: fused only)
+            _lib.check(self._L.mpcqp_fleet_loop_mixed(self._nominal._ws, self._relaxed._ws, ctypes.byref(self._fleet),
+                                                      self._bufs["cls"].data_ptr(), int(steps), s),
+                       "mpcqp_fleet_loop_mixed")
+            return
         if self.fused:
             _lib.check(self._L.mpcqp_fleet_loop(self._nominal._ws, self._relaxed._ws, ctypes.byref(self._fleet),
                                                 int(steps), s), "mpcqp_fleet_loop")

@@ -7,6 +7,12 @@ window + nominal QP (+ relaxed retry) + plant + path_idx/goal update) and, for s
 reference-style host loop (TrajectoryTracker.track, one B=1 solve per step) on one vehicle.
 
     python tools/fleet_bench.py [--vehicles 100 1024 4096] [--steps 100] [--horizon 15] [--fused]
+
+--classes K: a heterogeneous fleet (vehicle v runs under parameter block v mod K) in ONE launch
+(mpcqp_fleet_loop_mixed) against the same vehicles as K homogeneous fused sub-fleets launched back to
+back (mpcqp_fleet_loop each, --pairing applies to them); K = 1 measures the mixed kernel against the plain
+fused loop.  The two sides alternate within every repeat, first in one order, then in the other; the
+references are loaded before the timed window, which holds the loop launches up to a synchronise.
 """
 from __future__ import annotations
 
@@ -23,6 +29,93 @@ ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT / "rrt-mpc_amd"))
 
 
+def class_blocks(base, K):
+    """K parameter blocks of one horizon and dt: the base, then other wheelbases, limits and weights."""
+    from dataclasses import replace
+
+    pool = [
+        base,
+        replace(base, wheelbase_px=base.wheelbase_px * 4.0),  # the wheelbase at map_resolution 0.2
+        replace(base, u_bounds=((-5.0, 4.0), (-0.3, 0.25)), v_bounds=(2.0, 18.0), du_bounds=((-3.0, 2.5), (-0.05, 0.04))),
+        replace(base, q=np.array(base.q) * 2.0, q_terminal=np.array(base.q_terminal) * 2.0),
+        replace(base, r=np.array(base.r) * 4.0),
+        replace(base, v_bounds=(0.0, 12.0)),
+        replace(base, wheelbase_px=base.wheelbase_px * 2.0, du_bounds=((-8.0, 8.0), (-0.1, 0.1))),
+        replace(base, slack_velocity=1e4, slack_input=5e3, slack_rate=5e3),
+    ]
+    if not 1 <= K <= len(pool):
+        raise SystemExit(f"--classes takes 1..{len(pool)}")
+    return pool[:K]
+
+
+def mixed_bench(a) -> None:
+    """One mixed launch against K homogeneous fused sub-launches (see the module docstring)."""
+    import torch
+
+    from mpcqp import scenarios
+    from mpcqp.config import MPCConfig
+    from mpcqp.pipeline.fleet import FleetTracker
+
+    dev = torch.device("cuda:0")
+    K = a.classes
+    out = {"metric": "closed-loop vehicle-steps/s, loop launches only", "horizon": a.horizon, "sim_steps": a.steps,
+           "classes": K, "pairing_of_sub_fleets": a.pairing, "reps_per_order": a.reps, "runs": []}
+    mpc = MPCConfig(horizon=a.horizon, sim_steps=a.steps)
+    blocks = class_blocks(mpc.to_parameters(0.8), K)
+    for V in a.vehicles:
+        paths, starts, goals = scenarios.fleet5(V)
+        cls = np.arange(V) % K
+        groups = [np.flatnonzero(cls == c) for c in range(K)]
+        kw = dict(map_resolution=0.8, max_ref_len=160, device=dev, fused=True)
+        mixed = FleetTracker(mpc, max_vehicles=V, **kw)
+        mixed.set_classes(blocks)
+        subs = [FleetTracker(mpc, max_vehicles=len(g), params=blocks[c], pairing=a.pairing, **kw)
+                for c, g in enumerate(groups)]
+
+        def load():
+            mixed.reset_from_plans(paths, starts, goals, device_reference=True, classes=cls)
+            for ft, g in zip(subs, groups):
+                ft.reset_from_plans([paths[i] for i in g], starts[g], goals[g], device_reference=True)
+
+        def timed(fts):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for ft in fts:
+                ft.step(a.steps)
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0
+
+        times = {"mixed": [], "split": []}
+        for r in range(2 * a.reps + 1):  # repeat 0 warms up; then the order alternates
+            load()
+            order = ("mixed", "split") if r % 2 else ("split", "mixed")
+            for side in order:
+                dt = timed([mixed] if side == "mixed" else subs)
+                if r:
+                    times[side].append(dt)
+        rm = mixed.result()
+        steps_split = np.zeros(V, dtype=np.int64)
+        for ft, g in zip(subs, groups):
+            steps_split[g] = ft.result().steps
+        vsteps = int(rm.steps.sum())
+        run = {"vehicles": V, "vehicle_steps": vsteps, "same_step_counts": bool((steps_split == rm.steps).all()),
+               "goal_reached": int((rm.phase == 1).sum()), "aborted": int((rm.phase == 2).sum()),
+               "max_steps_of_a_vehicle": int(rm.steps.max())}
+        for side, ts in times.items():
+            run[side] = {"seconds_median": float(np.median(ts)), "seconds_min": min(ts), "seconds_max": max(ts),
+                         "seconds": ts, "value": vsteps / float(np.median(ts))}
+        run["mixed_over_split_time"] = run["mixed"]["seconds_median"] / run["split"]["seconds_median"]
+        # per class: vehicle-steps and the longest vehicle (what sets a sub-launch's tail)
+        run["per_class"] = [{"vehicles": len(g), "vehicle_steps": int(rm.steps[g].sum()),
+                             "max_steps": int(rm.steps[g].max())} for g in groups]
+        out["runs"].append(run)
+        mixed.close()
+        for ft in subs:
+            ft.close()
+        print(json.dumps(run), flush=True)
+    print(json.dumps(out))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--vehicles", type=int, nargs="+", default=[100, 1024, 4096])
@@ -32,7 +125,12 @@ def main() -> None:
     ap.add_argument("--fused", action="store_true", help="mpcqp_fleet_loop: one launch for the whole loop")
     ap.add_argument("--pairing", default="auto", choices=["auto", "on", "off"],
                     help="two vehicles per wave for N <= 15 (mpcqp_set_pairing)")
+    ap.add_argument("--classes", type=int, default=0,
+                    help="K > 0: one mixed fused launch (mpcqp_fleet_loop_mixed) against K homogeneous fused launches")
     a = ap.parse_args()
+    if a.classes:
+        mixed_bench(a)
+        return
     import torch
 
     from mpcqp import scenarios
