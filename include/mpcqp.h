@@ -183,6 +183,37 @@ int mpcqp_solve(mpcqp_ws* ws, int B, double* u0, double* X, double* U, int32_t* 
                 int32_t* iters, uint8_t* active, void* stream);
 
 /*
+ * mpcqp_solve from a caller's guess (additive to ABI 9): the warm start of a closed loop, where the QP
+ * of step k + 1 is nearly that of step k and the previous U, shifted one step, is close to the optimum.
+ *   U_guess  B x 2 x N (device), the layout of the U output: accelerations, then steering angles
+ * The polish (a semismooth Newton on the active set) returns the exact optimum from wherever it
+ * converges, so the guess is one polish attempt BEFORE ADMM, not a new ADMM state:
+ *   unusable  any of the QP's 2N entries non-finite, or guess_passes <= 0: the QP is solved cold, and
+ *             every output, iters included, is mpcqp_solve's bit for bit.
+ *   attempt   otherwise, after the usual setup: speeds v_{k+1} = x0[3] + dt sum_{j<=k} a_j, the steering
+ *             angles as they are, scaled into the solver's variables; one polish from that point of at
+ *             most min(guess_passes, polish_max_iter) passes (whatever the `polish` switch says: that
+ *             one governs the polish after ADMM).  Method ADMM only: MPCQP_METHOD_NEWTON ignores the guess.
+ *   hit       the attempt converged: status MPCQP_SOLVED at the exact optimum, iters[0] == 0 (no ADMM
+ *             factorization, no ADMM iteration), iters[1..3] count the attempt.
+ *   miss      it did not, for whatever reason (a numerical failure of the attempt is a miss, not
+ *             MPCQP_NUMERICAL_ERROR): the cold solve runs from its usual initial state; u0, X, U, status
+ *             and active are mpcqp_solve's bit for bit, iters[0] is the cold value, iters[1..3] the cold
+ *             values plus the attempt's.
+ * So a bad guess never changes an answer, it only costs the attempt; no loop is unbounded.  A hit and a
+ * cold solve of the same QP both return the exact optimum, computed along different paths: warm results
+ * equal cold ones to rounding, not bit for bit.
+ * Solves the last plain mpcqp_build of the same B: MPCQP_E_STATE without one, and after
+ * mpcqp_build_mixed.  NULL U_guess or status: MPCQP_E_ARG.  The fused one-wave kernel only (N <= 32,
+ * fast mode, no debug_state; one QP per wave whatever mpcqp_set_pairing says): other parameter blocks
+ * return MPCQP_E_HORIZON.  In every error case nothing is enqueued and nothing is written.  U_guess must
+ * stay valid until the solve has run (stream order); it may be the U output itself (each wave reads
+ * its row before it writes it).
+ */
+int mpcqp_solve_warm(mpcqp_ws* ws, int B, const double* U_guess, int guess_passes, double* u0, double* X, double* U,
+                     int32_t* status, int32_t* iters, uint8_t* active, void* stream);
+
+/*
  * B = 1 low-latency path (ABI 7): the sequential closed loop of TrajectoryTracker.track solves one QP
  * per step (control_stage.py:100-129), where host overhead, not the kernel, decides the step time.
  * The workspace owns two blocks of pinned, device-mapped, coherent host memory and a private
@@ -342,6 +373,21 @@ int mpcqp_fleet_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f,
  * model input in the three mixed solve kernels), the swarm, and the B = 1 paths. */
 int mpcqp_fleet_loop_mixed(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const int32_t* cls, int steps,
                            void* stream);
+
+/* mpcqp_fleet_loop with a warm start (additive to ABI 9): inside the launch each vehicle keeps the U of
+ * its accepted solve, and both solves of its next step (the nominal one and the relaxed retry) start
+ * from it, shifted one step down with the last step repeated, under mpcqp_solve_warm's contract (one
+ * polish attempt of at most guess_passes passes; a miss runs the cold solve unchanged).  A vehicle's
+ * first step in a launch is cold: a run split over several launches restarts cold at each launch.
+ * With guess_passes <= 0 every buffer equals mpcqp_fleet_loop's (one vehicle per wave) bit for bit; with
+ * a warm start the buffers equal the cold loop's to rounding only, as each step's optimum does.
+ * Argument checks, the device's validation of the loop state, the exits, the longest-first dispatch and
+ * the invalidation of both workspaces' builds are mpcqp_fleet_loop's.  The fused loop only -- N <= 32 in
+ * fast mode without debug_state; other parameter blocks return MPCQP_E_HORIZON, and then nothing is
+ * enqueued and nothing invalidated.  One vehicle per wave whatever mpcqp_set_pairing says; the replan
+ * trigger is off.  Out of scope: the stepped fleet, mixed classes and the swarm. */
+int mpcqp_fleet_loop_warm(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, int steps, int guess_passes,
+                          void* stream);
 
 /*
  * Batched build_reference: src/control/ref_builder.py:10-22 with

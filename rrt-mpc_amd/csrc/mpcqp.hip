@@ -221,6 +221,10 @@ fleet_loop_mixed_t fleet_looper_mixed(const mpcqp_params& p) {
   const HorizonKernels* k = one_wave(p, false);
   return k ? k->loop_mixed : nullptr;
 }
+fleet_loop_warm_t fleet_looper_warm(const mpcqp_params& p) {
+  const HorizonKernels* k = one_wave(p, false);
+  return k ? k->loop_warm : nullptr;
+}
 }  // namespace mpcqp
 
 extern "C" {
@@ -413,6 +417,29 @@ int mpcqp_solve(mpcqp_ws* ws, int B, double* u0, double* X, double* U, int32_t* 
   }
   (L.ref && mpcqp::use_pairs(ws, B) ? g_kernels[ws->p.horizon].pair : mpcqp::launcher(ws->p))(s, L);
   return mpcqp::launched("k_solve");
+}
+
+int mpcqp_solve_warm(mpcqp_ws* ws, int B, const double* U_guess, int guess_passes, double* u0, double* X, double* U,
+                     int32_t* status, int32_t* iters, uint8_t* active, void* stream) {
+  if (!ws || !status || !U_guess) return fail(MPCQP_E_ARG, "null argument");
+  // the fused one-wave kernel only; refused before anything is enqueued
+  const mpcqp::HorizonKernels* k = mpcqp::one_wave(ws->p, false);
+  if (!k || !k->warm)
+    return fail(MPCQP_E_HORIZON, "mpcqp_solve_warm runs the fused one-wave kernel only (N <= 32, fast mode, no "
+                                 "debug_state)");
+  const mpcqp_ws::Build& built = ws->build;
+  if (!built.valid || B < 0 || B != built.B)
+    return fail(MPCQP_E_STATE, "mpcqp_solve_warm B differs from the last mpcqp_build");
+  if (built.cls) return fail(MPCQP_E_STATE, "mpcqp_solve_warm after mpcqp_build_mixed: it solves a plain mpcqp_build");
+  if (B == 0) return MPCQP_OK;
+  Launch L{&ws->p, B, nullptr, nullptr, u0, X, U, status, iters, active, nullptr};
+  L.x0 = built.x0;  // the build of a one-wave workspace without debug_state is fused: the caller's inputs
+  L.ref = built.ref;
+  L.u_prev = built.u_prev;
+  L.guess = U_guess;
+  L.guess_passes = guess_passes;
+  k->warm(static_cast<hipStream_t>(stream), L);
+  return mpcqp::launched("k_solve_warm");
 }
 
 // ------------------------------------------------------------------ B = 1 path

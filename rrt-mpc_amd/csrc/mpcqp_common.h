@@ -488,6 +488,9 @@ struct Launch {
   const mpcqp_params* table = nullptr;
   const int32_t* cls = nullptr;
   int K = 0;
+  // a caller's guess (mpcqp_solve_warm): B x 2 x N in the layout of U, and the attempt's pass limit
+  const double* guess = nullptr;
+  int guess_passes = 0;
 };
 
 typedef void (*launcher_t)(hipStream_t, const Launch&);
@@ -531,10 +534,13 @@ typedef void (*fleet_loop_t)(hipStream_t, const mpcqp_params*, const mpcqp_fleet
 // fleet, steps, the dispatch order (or nullptr)
 typedef void (*fleet_loop_mixed_t)(hipStream_t, const mpcqp_params*, const int32_t*, int, const mpcqp_fleet&, int,
                                    const int32_t*);
+// the warm-started fused loop: the two blocks, the fleet, steps, guess_passes, the dispatch order (or nullptr)
+typedef void (*fleet_loop_warm_t)(hipStream_t, const mpcqp_params*, const mpcqp_fleet&, int, int, const int32_t*);
 // The kernels of one horizon of the one-wave family (N < MPCQP_WIDE_MIN_HORIZON; the launch_*<N>
 // templates of mpcqp_solve.h): k_solve, k_solve_mixed (a parameter block per QP), k_solve_pair (two
 // QPs per wave, fused K1; nullptr above kPairMaxHorizon), k_serve (the B = 1 server), k_fleet_loop
-// (the fused closed loop) and k_fleet_loop_mixed (the same with a class per vehicle).  The object that
+// (the fused closed loop), k_fleet_loop_mixed (the same with a class per vehicle), k_solve_warm (from a
+// caller's guess) and k_fleet_loop_warm (the fused loop, each step from the one before).  The object that
 // instantiates a horizon registers it from a namespace-scope
 // initialiser (register_horizons, mpcqp_solve.h); an all-null entry is a horizon not compiled in.
 struct HorizonKernels {
@@ -542,6 +548,8 @@ struct HorizonKernels {
   serve_t serve;
   fleet_loop_t loop;
   fleet_loop_mixed_t loop_mixed;
+  launcher_t warm;
+  fleet_loop_warm_t loop_warm;
 };
 // fills entry N of the table in mpcqp.hip (constant-initialised, so the order of the objects'
 // initialisers does not matter)
@@ -549,6 +557,7 @@ void register_horizon(int N, const HorizonKernels& k);
 // nullptr when the parameter block does not run the one-wave kernel; defined in mpcqp.hip
 fleet_loop_t fleet_looper(const mpcqp_params& p);
 fleet_loop_mixed_t fleet_looper_mixed(const mpcqp_params& p);
+fleet_loop_warm_t fleet_looper_warm(const mpcqp_params& p);
 // k_solve_pair / k_fleet_loop<N, true> for `count` QPs or vehicles of this workspace's launch?
 bool use_pairs(const mpcqp_ws* ws, int count);
 // the long-horizon solve (N >= MPCQP_WIDE_MIN_HORIZON; mpcqp_wide.hip): one 256-thread workgroup

@@ -355,6 +355,30 @@ int mpcqp_fleet_loop_mixed(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fle
   return mpcqp::launched("k_fleet_loop_mixed");
 }
 
+int mpcqp_fleet_loop_warm(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, int steps, int guess_passes,
+                          void* stream) {
+  int rc = check_fleet(nominal, relaxed, f);
+  if (rc) return rc;
+  if (steps < 0) return fail(MPCQP_E_ARG, "steps must be >= 0");
+  // the fused one-wave kernel only; refused before anything is enqueued or invalidated
+  const mpcqp::fleet_loop_warm_t loop = mpcqp::fleet_looper_warm(nominal->p);
+  if (!loop || mpcqp::fleet_looper_warm(relaxed->p) != loop)
+    return fail(MPCQP_E_HORIZON, "mpcqp_fleet_loop_warm runs the fused one-wave loop only (N <= 32, fast mode, no "
+                                 "debug_state): the stepped fleet takes no guess");
+  if (f->vehicles == 0 || steps == 0) return MPCQP_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  nominal->invalidate();  // as mpcqp_fleet_loop: a later mpcqp_solve needs its own build
+  relaxed->invalidate();
+  hipLaunchKernelGGL(k_store_params, dim3(1), dim3(kWave), 0, s, nominal->p, relaxed->p, nominal->dparams);
+  const int32_t* order = nullptr;
+  if (nominal->cus > 0 && f->vehicles > 8 * nominal->cus) {  // longest first, as mpcqp_fleet_loop
+    hipLaunchKernelGGL(k_fleet_order, dim3(1), dim3(kOrderBuckets), 0, s, *f, nominal->dorder);
+    order = nominal->dorder;
+  }
+  loop(s, nominal->dparams, *f, steps, guess_passes, order);
+  return mpcqp::launched("k_fleet_loop_warm");
+}
+
 int mpcqp_fleet_run(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, int steps, int use_graph,
                     void* stream) {
   int rc = check_fleet(nominal, relaxed, f);

@@ -1357,14 +1357,22 @@ __device__ __forceinline__ int polish_qp(Ctx<N, Pair>& C, double& x, const doubl
 // attempts the polish: an exact optimum found there satisfies the termination test itself.
 // admm_run stops at such an attempt with its loop state in the caller's AdmmState (mpcqp_common.h, with
 // the events it returns), and the driver (solve_one, k_solve) polishes and resumes it after a failed one.
-template <int N, bool Pair = false>
-__device__ __forceinline__ int admm_run(const mpcqp_params& p, Ctx<N, Pair>& C, AdmmState& S) {
+// CanPass / pass (the warm start's first trip, solve_one): nothing runs, S goes to a polish attempt as
+// it stands.  A template switch, so that the instantiations without it are the code they were.
+template <int N, bool Pair = false, bool CanPass = false>
+__device__ __forceinline__ int admm_run(const mpcqp_params& p, Ctx<N, Pair>& C, AdmmState& S, bool pass = false) {
   using LN = Lanes<Pair>;
   const bool act = C.act;
   const double sg = p.sigma, alpha = p.alpha;
   const bool early = p.polish != 0 && p.polish_from > 0;
   int ev = kAdmmMaxIter;
   bool done = false;
+  if constexpr (CanPass) {
+    if (pass) {
+      ev = kAdmmAttempt;
+      done = true;
+    }
+  }
   Stamps T;
   while (S.it < p.max_iter && !done) {
     if (S.need_fact) {
@@ -1707,16 +1715,63 @@ __device__ __forceinline__ int finish_qp(const mpcqp_params& p, int b, const dou
   return status;
 }
 
+// GuessWin: a batch with a caller's guess (k_solve_warm): the caller's buffers exactly as BatchWin; a
+// type of its own for ClassWin's reason.
+struct GuessWin {
+  static constexpr bool kFleet = false;
+  __device__ __forceinline__ int lane() const { return threadIdx.x; }
+};
+
+// A caller's guess in the solver's variables.  g: the lane's entry of a U in the output layout (lane
+// c N + k holds U[c][k]: accelerations on the speed lanes, steering angles after them); v0 = x0[3].  The
+// speeds v_{k+1} = v0 + dt sum_{j <= k} a_j (finish_qp's a_k = (v_{k+1} - v_k) / dt, inverted), the
+// steering angles as they are; x = W / D (finish_qp's W = D x).  Lanes past the variables: 0.
+template <int N, bool Pair>
+__device__ __forceinline__ double guess_lane(double g, int lane, double v0, double dt, double D) {
+  using LN = Lanes<Pair>;
+  const bool act = lane < 2 * N, even = lane < N;
+  const double acc = LN::scan(even ? g : 0.0, lane);
+  const double W = even ? v0 + dt * acc : g;
+  return act ? W / D : 0.0;
+}
+
+// The warm start's state in solve_one: the lane's entry of the guess, the attempt's pass limit, and
+// where the guess's trip of the driver loop stands.  A cold solve carries the empty one, whose flags
+// are constants: it declares no variable of its own in solve_one, where even an unused local changes
+// the register allocation of the kernels that were there before.
+template <bool Warm>
+struct Guess {
+  double lane = 0.0;
+  int passes = 0;
+  bool pending = false;  // the guess is usable and its trip is still to come
+  bool now = false;      // this trip is the guess's attempt (the first one, S.it == 0)
+};
+template <>
+struct Guess<false> {
+  static constexpr int passes = 0;
+  static constexpr bool pending = false, now = false;
+};
+
 // One QP through setup -> ADMM (+ early polish attempts) -> final polish -> outputs on the calling
 // wave, for k_solve_pair, k_solve_mixed, k_fleet_loop and k_serve (no debug state): returns the status,
 // Ulane = the lane's U entry (lanes 0 and N: u0).  k_solve runs the same driver inline (below).
-template <int N, class Win, bool Pair = false>
+// Warm (k_solve_warm, k_fleet_loop_warm; fused K1 only): g.lane is the lane's entry of a caller's U
+// (guess_lane).  A usable guess (every entry finite, g.passes > 0, method ADMM) gets one polish
+// of at most min(g.passes, polish_max_iter) passes before ADMM, as the loop's first trip: the
+// polish returns the exact optimum from wherever it converges, so a hit ends the solve with no ADMM
+// factorization and no ADMM iteration (iters[0] == 0).  The guess enters as the ADMM state's x (z = Cbar
+// x), which admm_run passes to the polish untouched on that trip, so the attempt is an early attempt like
+// any other to the code around it (a branch of its own around admm_run cost the kernel 350 bytes of
+// scratch at N = 20).  A miss, for whatever reason, puts S back as it was initialised (the attempt also
+// wrote the inverse's registers, which need_fact = true recomputes): the cold solve runs on the same
+// values, and only the polish counters carry the attempt's passes on top of its own.
+template <int N, class Win, bool Pair = false, bool Warm = false>
 __device__ __forceinline__ int solve_one(const mpcqp_params& p, int b, const double* __restrict__ model,
                                          const double* __restrict__ in_x0, const double* __restrict__ in_ref,
                                          const double* __restrict__ in_up, const Win& win, SolveLds<N, Pair>& sm,
                                          double* __restrict__ u0o, double* __restrict__ Xo, double* __restrict__ Uo,
                                          int32_t* __restrict__ statuso, int32_t* __restrict__ iterso,
-                                         uint8_t* __restrict__ activeo, double& Ulane) {
+                                         uint8_t* __restrict__ activeo, double& Ulane, Guess<Warm> g = {}) {
   double* const dbg = nullptr;
   const uint64_t t_start = __builtin_amdgcn_s_memtime();
   Stamps TK;
@@ -1737,14 +1792,32 @@ __device__ __forceinline__ int solve_one(const mpcqp_params& p, int b, const dou
   double x = 0.0, x_admm = 0.0;
   bool do_polish = false, pol_ok = false;
   if (use_admm && bad) admm_debug_state<N>(dbg, C.act, 0.0, flag, 0, 0);
+  // warm: a usable guess is the ADMM state's x (with z = Cbar x) for the first trip, in which admm_run
+  // only hands it to the polish
+  if constexpr (Warm) {
+    g.pending = use_admm && g.passes > 0 && !Lanes<Pair>::any(C.act && !isfinite(g.lane));
+    if (g.pending) {
+      double v0;
+      if constexpr (Win::kFleet) v0 = win.x0v(3);
+      else v0 = in_x0[(size_t)b * 4 + 3];
+      S.x = guess_lane<N, Pair>(g.lane, win.lane(), v0, p.dt, C.D);
+      C.Cmul(S.x, S.z);
+    }
+  }
   // ADMM with its early polish attempts, then the final polish: ONE polish call site
   while (!bad) {
     // kind 1: early attempt (ADMM resumes if it fails), 2: final polish (OSQP polishes only a
     // solved ADMM run; method newton is the polish alone, from x = 0)
     int kind = 0;
     double zg[3];
+    if constexpr (Warm) {
+      g.now = g.pending;
+      g.pending = false;
+    }
     if (use_admm) {
-      const int ev = admm_run<N, Pair>(p, C, S);
+      int ev;
+      if constexpr (Warm) ev = admm_run<N, Pair, true>(p, C, S, g.now);
+      else ev = admm_run<N, Pair>(p, C, S);
       if (ev == kAdmmAttempt) {
         kind = 1;
       } else {
@@ -1766,8 +1839,12 @@ __device__ __forceinline__ int solve_one(const mpcqp_params& p, int b, const dou
     double xp = kind == 1 ? S.x : x;
     Stamps T2;
     T2.begin();
-    const int r_ = polish_qp<N, Pair>(C, xp, zg, kind == 1 ? p.polish_attempt_max_iter : p.polish_max_iter, pol_it,
-                                S.nfact, n_ls);
+    // the pass limit: the guess's attempt min(g.passes, polish_max_iter), an early attempt its own
+    const int r_ = polish_qp<N, Pair>(C, xp, zg,
+                                      (Warm && g.now) ? min(g.passes, p.polish_max_iter)
+                                      : kind == 1          ? p.polish_attempt_max_iter
+                                                           : p.polish_max_iter,
+                                      pol_it, S.nfact, n_ls);
     T2.end(0);
     T2.flush(12);  // g_stamps[12]: polish
     if (kind == 2) {  // final polish: its iterate is returned when it converged
@@ -1776,7 +1853,8 @@ __device__ __forceinline__ int solve_one(const mpcqp_params& p, int b, const dou
       pol_ok = r_ > 0;
       break;
     }
-    if (r_ != 0) {  // the attempt reached the exact optimum (ADMM flag 2) or failed numerically
+    // a numerical failure of the guess's attempt is a miss like any other: the cold solve follows
+    if (r_ != 0 && !(Warm && g.now && r_ < 0)) {  // the attempt reached the exact optimum (ADMM flag 2) or failed numerically
       flag = r_ > 0 ? 2 : kAdmmBad;
       bad = r_ < 0;
       pol_ok = r_ > 0;
@@ -1789,6 +1867,11 @@ __device__ __forceinline__ int solve_one(const mpcqp_params& p, int b, const dou
     S.need_fact = true;
     if (S.rho_change) S.rho = S.rho_next;
     S.rho_change = false;
+    if (Warm && g.now) {  // a miss: S as it was initialised, for the cold solve
+      S.x = 0.0;
+#pragma unroll
+      for (int r = 0; r < 3; ++r) S.z[r] = 0.0;
+    }
   }
   const int status = finish_qp<N, Win, Pair>(p, b, model, in_x0, in_ref, in_up, win, sm.model, C, x, x_admm, flag, do_polish, pol_ok, bad, S.it,
                                   S.nfact, pol_it, n_ls, u0o, Xo, Uo, statuso, iterso, activeo, Ulane);
@@ -1990,6 +2073,30 @@ __global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_solve_mixed(cons
                          U);
 }
 
+// ------------------------------------------------------------------ K2 from a caller's guess
+// mpcqp_solve_warm: QP b starts from row b of U_guess (B x 2 x N, the layout of the U output) through
+// solve_one's warm driver: one polish attempt from the guess, and the cold solve of k_solve where it
+// misses or the guess is unusable -- then k_solve's results bit for bit.  One QP per wave, fused K1.
+// U_guess may be the U output itself: the wave reads its row here, before anything is written.
+template <int N>
+__global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_solve_warm(mpcqp_params p, int B,
+                                                      const double* __restrict__ in_x0,
+                                                      const double* __restrict__ in_ref,
+                                                      const double* __restrict__ in_up, const double* U_guess,
+                                                      int guess_passes, double* __restrict__ u0o,
+                                                      double* __restrict__ Xo, double* Uo,
+                                                      int32_t* __restrict__ statuso, int32_t* __restrict__ iterso,
+                                                      uint8_t* __restrict__ activeo) {
+  __shared__ SolveLds<N> sm;
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  const int lane = threadIdx.x;
+  const double g = lane < 2 * N ? U_guess[(size_t)b * (2 * N) + lane] : 0.0;
+  double U;
+  solve_one<N, GuessWin, false, true>(p, b, nullptr, in_x0, in_ref, in_up, GuessWin{}, sm, u0o, Xo, Uo, statuso,
+                                      iterso, activeo, U, Guess<true>{g, guess_passes});
+}
+
 // ------------------------------------------------------------------ fused closed loop
 // Every vehicle of a fleet runs `steps` iterations of the loop body of TrajectoryTracker.track
 // (control_stage.py:100-150) on its own wave, with no kernel boundary between steps: the window
@@ -2004,10 +2111,12 @@ __global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_solve_mixed(cons
 // fleet_loop_body: the loop of one vehicle b (< V) on its wave or half-wave, shared by k_fleet_loop and
 // k_fleet_loop_mixed (which hands in P offset to the vehicle's pair of blocks).  ls: the vehicle's six
 // doubles of loop state in LDS, sm its solver LDS.
-template <int N, bool Pair>
+// Warm (k_fleet_loop_warm): each solve of a step starts from the U of the step before, shifted one step
+// down (solve_one's warm driver); Ug, that U's lane value, is the only state it adds to the step loop.
+template <int N, bool Pair, bool Warm = false>
 __device__ __forceinline__ void fleet_loop_body(const mpcqp_params* __restrict__ P, const mpcqp_fleet& f, int steps,
                                                 const mpcqp::LoopTrigger& tr, int b, int lane,
-                                                SolveLds<N, Pair>& sm, double* const ls) {
+                                                SolveLds<N, Pair>& sm, double* const ls, int guess_passes = 0) {
   using LN = Lanes<Pair>;
   const int V = f.vehicles;
   int phase = f.phase[b];
@@ -2036,6 +2145,9 @@ __device__ __forceinline__ void fleet_loop_body(const mpcqp_params* __restrict__
   if (lane < 4) ls[lane] = f.state[(size_t)b * 4 + lane];
   else if (lane < 6) ls[lane] = f.u_prev[(size_t)b * 2 + lane - 4];
   __syncthreads();
+  // warm: the accepted solve's U of the step before, by lane; NaN (no step yet in this launch) is an
+  // unusable guess, so a vehicle's first step is cold
+  [[maybe_unused]] double Ug = __builtin_nan("");
   for (int s = 0; s < steps; ++s) {
     // k_fleet_build's validation of the loop state, before any indexed access
     const bool bad_ref = len < 1 || len > f.ref_stride || pidx < 0;
@@ -2057,14 +2169,28 @@ __device__ __forceinline__ void fleet_loop_body(const mpcqp_params* __restrict__
       const mpcqp_params& p = P[relax];  // P = {nominal, relaxed} in global memory (ws->dparams)
       FleetWin win{rows, ln, len, pidx, relax != 0, {ls[0], ls[1], ls[2], ls[3]}, {ls[4], ls[5]}};
       double Ul;
-      const int st = solve_one<N, FleetWin, Pair>(p, b, nullptr, nullptr, nullptr, nullptr, win, sm,
-                                                  f.u0 + (size_t)relax * V * 2, f.X, nullptr,
-                                                  f.status + (size_t)relax * V, nullptr, nullptr, Ul);
+      int st;
+      if constexpr (Warm) {
+        // the guess: the last U one step on (lane j <- j + 1 within each block, the last step repeated);
+        // the nominal solve and the relaxed retry start from the same one
+        double up = LN::shl1(Ug);
+        asm volatile("" : "+v"(up));  // pinned: the shift runs on every lane, not inside the select below
+        const double g = (ln == N - 1 || ln == 2 * N - 1) ? Ug : up;
+        st = solve_one<N, FleetWin, Pair, true>(p, b, nullptr, nullptr, nullptr, nullptr, win, sm,
+                                                f.u0 + (size_t)relax * V * 2, f.X, nullptr,
+                                                f.status + (size_t)relax * V, nullptr, nullptr, Ul,
+                                                Guess<true>{g, guess_passes});
+      } else {
+        st = solve_one<N, FleetWin, Pair>(p, b, nullptr, nullptr, nullptr, nullptr, win, sm,
+                                          f.u0 + (size_t)relax * V * 2, f.X, nullptr,
+                                          f.status + (size_t)relax * V, nullptr, nullptr, Ul);
+      }
       __syncthreads();  // the next solve (or step) reuses the LDS
       if (lane == 0) f.mask[(size_t)relax * V + b] = 1;
       if (st == MPCQP_SOLVED || st == MPCQP_SOLVED_INACCURATE) {
         which = relax;
         U = Ul;
+        if constexpr (Warm) Ug = Ul;
         break;
       }
     }
@@ -2173,6 +2299,24 @@ __global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_fleet_loop_mixed
   fleet_loop_body<N, false>(P + 2 * (size_t)c, f, steps, off, b, lane, sm, ls);
 }
 
+// ------------------------------------------------------------------ fused closed loop, warm started
+// mpcqp_fleet_loop_warm: k_fleet_loop<N>'s body with each step's solves started from the step before
+// (fleet_loop_body's Warm).  One vehicle per wave, no replan trigger; the first step of a launch is
+// cold, and with guess_passes <= 0 every step is: k_fleet_loop<N>'s buffers bit for bit.
+template <int N>
+__global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_fleet_loop_warm(const mpcqp_params* __restrict__ P,
+                                                                              mpcqp_fleet f, int steps,
+                                                                              int guess_passes,
+                                                                              const int32_t* __restrict__ order) {
+  __shared__ SolveLds<N> sm;
+  __shared__ double ls[6];  // loop state: x[4], u_prev[2]
+  const int b = order ? order[blockIdx.x] : (int)blockIdx.x;
+  const int lane = (int)threadIdx.x;
+  if (b < 0 || b >= f.vehicles) return;
+  const mpcqp::LoopTrigger off{0.0, 0, nullptr, nullptr};
+  fleet_loop_body<N, false, true>(P, f, steps, off, b, lane, sm, ls, guess_passes);
+}
+
 // ------------------------------------------------------------------ B = 1 server
 // One resident wave serving the sequential closed loop of TrajectoryTracker.track: it waits for the
 // host to raise box->req (system-scope loads of pinned host memory, s_sleep between polls), solves the
@@ -2247,6 +2391,17 @@ void launch_fleet_loop_mixed(hipStream_t s, const mpcqp_params* P, const int32_t
                              int steps, const int32_t* order) {
   hipLaunchKernelGGL(k_fleet_loop_mixed<N>, dim3(f.vehicles), dim3(kWave), 0, s, P, cls, K, f, steps, order);
 }
+// from a caller's guess (L.guess, L.guess_passes; fused K1, no debug state)
+template <int N>
+void launch_solve_warm(hipStream_t s, const Launch& L) {
+  hipLaunchKernelGGL(k_solve_warm<N>, dim3(L.B), dim3(kWave), 0, s, *L.p, L.B, L.x0, L.ref, L.u_prev, L.guess,
+                     L.guess_passes, L.u0, L.X, L.U, L.st, L.it, L.ac);
+}
+template <int N>
+void launch_fleet_loop_warm(hipStream_t s, const mpcqp_params* P, const mpcqp_fleet& f, int steps, int guess_passes,
+                            const int32_t* order) {
+  hipLaunchKernelGGL(k_fleet_loop_warm<N>, dim3(f.vehicles), dim3(kWave), 0, s, P, f, steps, guess_passes, order);
+}
 // two QPs per wave (N <= kPairMaxHorizon, fused K1, no debug state)
 template <int N>
 void launch_solve_pair(hipStream_t s, const Launch& L) {
@@ -2261,7 +2416,7 @@ void launch_solve_pair(hipStream_t s, const Launch& L) {
 template <int LO, int HI>
 int register_horizons() {
   HorizonKernels k{&launch_solve<LO>, &launch_solve_mixed<LO>, nullptr, &launch_serve<LO>, &launch_fleet_loop<LO>,
-                   &launch_fleet_loop_mixed<LO>};
+                   &launch_fleet_loop_mixed<LO>, &launch_solve_warm<LO>, &launch_fleet_loop_warm<LO>};
   if constexpr (LO <= kPairMaxHorizon) k.pair = &launch_solve_pair<LO>;
   register_horizon(LO, k);
   if constexpr (LO < HI) return register_horizons<LO + 1, HI>();

@@ -41,6 +41,8 @@ ABI_VERSION = 9  # MPCQP_ABI_VERSION (include/mpcqp.h)
 PAIR_OFF, PAIR_ON, PAIR_AUTO = 0, 1, 2
 PAIRING_MODES = {"off": PAIR_OFF, "on": PAIR_ON, "auto": PAIR_AUTO}
 E_DEVICE = -6  # MPCQP_E_DEVICE: a fault surfaced at a stream synchronisation
+# warm start (mpcqp_solve_warm, mpcqp_fleet_loop_warm): polish passes the guess's attempt may take
+DEFAULT_GUESS_PASSES = 8  # the best of 1, 2, 3, 5, 8 at 4096 vehicles, N = 20 (profiles/warm_start/)
 
 DEFAULT_SOLVER_SETTINGS = dict(
     rho=0.1,
@@ -319,6 +321,10 @@ _SYMBOLS = {
     "mpcqp_set_pairing": ([ctypes.c_void_p, ctypes.c_int], ctypes.c_int),
     "mpcqp_set_classes": ([ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(MpcqpParams)], ctypes.c_int),
     "mpcqp_build_mixed": ([ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5, ctypes.c_int),
+    "mpcqp_solve_warm": ([ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 7,
+                         ctypes.c_int),
+    "mpcqp_fleet_loop_warm": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MpcqpFleet), ctypes.c_int,
+                               ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
 }
 
 

@@ -229,10 +229,18 @@ class BatchedMPCController:
             t = t.reshape(shape)
         return t
 
-    def solve_batch(self, x0, ref, u_prev=None, *, stream=None, classes=None) -> BatchSolution:
+    def solve_batch(self, x0, ref, u_prev=None, *, stream=None, classes=None, U_guess=None,
+                    guess_passes=None) -> BatchSolution:
         """``classes`` (int array or int32 device tensor of shape (B,)): QP b is solved under block
         ``classes[b]`` of ``set_classes``; a QP whose index lies outside the table reports status
-        ``_lib.BAD_CLASS`` and none of its other outputs is written.  ``None``: the controller's block."""
+        ``_lib.BAD_CLASS`` and none of its other outputs is written.  ``None``: the controller's block.
+
+        ``U_guess`` (tensor or array of shape (B, 2, N), the layout of ``U``): warm start
+        (``mpcqp_solve_warm``) -- each QP first gets one polish attempt of at most ``guess_passes``
+        passes (default ``_lib.DEFAULT_GUESS_PASSES``) from its guess; a hit returns the exact optimum
+        with ``iters[:, 0] == 0``, a miss or an unusable guess (a non-finite entry, ``guess_passes <= 0``)
+        runs the cold solve unchanged.  The previous ``U`` shifted one step is the usual guess; the
+        returned ``U`` tensor itself may be passed.  Not with ``classes``; horizons <= 32 in fast mode."""
         torch = self._torch
         N = self.horizon
         B = int(x0.shape[0])
@@ -240,6 +248,12 @@ class BatchedMPCController:
             raise ValueError(f"batch {B} exceeds max_batch {self.max_batch}")
         if classes is not None and not self.num_classes:
             raise ValueError("solve_batch(classes=...) needs a class table: call set_classes first")
+        if U_guess is not None and classes is not None:
+            raise ValueError("solve_batch(U_guess=...) does not take classes: the warm start solves a plain batch")
+        if U_guess is None and guess_passes is not None:
+            raise ValueError("solve_batch(guess_passes=...) needs U_guess")
+        if U_guess is not None and tuple(U_guess.shape) != (B, 2, N):
+            raise ValueError(f"U_guess must have shape ({B}, 2, {N}), got {tuple(U_guess.shape)}")
         cls_t = None if classes is None else self._class_input(classes, B)
         x0_t = self._device_input(x0, (B, 4), "x0")
         if len(ref.shape) == 3 and ref.shape[1] > N + 1:  # rows past N are never read (see solve)
@@ -249,7 +263,8 @@ class BatchedMPCController:
         if stream is None:
             stream = torch.cuda.current_stream(self.device)
         s = ctypes.c_void_p(stream.cuda_stream)
-        self._keep = (x0_t, ref_t, up_t, cls_t)  # keep inputs alive until the kernels have consumed them
+        ug_t = None if U_guess is None else self._device_input(U_guess, (B, 2, N), "U_guess")
+        self._keep = (x0_t, ref_t, up_t, cls_t, ug_t)  # keep inputs alive until the kernels have consumed them
         if cls_t is None:
             _lib.check(self._L.mpcqp_build(self._ws, B, x0_t.data_ptr(), ref_t.data_ptr(),
                                            None if up_t is None else up_t.data_ptr(), s), "mpcqp_build")
@@ -257,9 +272,16 @@ class BatchedMPCController:
             _lib.check(self._L.mpcqp_build_mixed(self._ws, B, x0_t.data_ptr(), ref_t.data_ptr(),
                                                  None if up_t is None else up_t.data_ptr(), cls_t.data_ptr(), s),
                        "mpcqp_build_mixed")
-        _lib.check(self._L.mpcqp_solve(self._ws, B, self._u0.data_ptr(), self._X.data_ptr(), self._U.data_ptr(),
-                                       self._status.data_ptr(), self._iters.data_ptr(), self._active.data_ptr(), s),
-                   "mpcqp_solve")
+        if ug_t is not None:
+            passes = _lib.DEFAULT_GUESS_PASSES if guess_passes is None else int(guess_passes)
+            _lib.check(self._L.mpcqp_solve_warm(self._ws, B, ug_t.data_ptr(), passes, self._u0.data_ptr(),
+                                                self._X.data_ptr(), self._U.data_ptr(), self._status.data_ptr(),
+                                                self._iters.data_ptr(), self._active.data_ptr(), s),
+                       "mpcqp_solve_warm")
+        else:
+            _lib.check(self._L.mpcqp_solve(self._ws, B, self._u0.data_ptr(), self._X.data_ptr(), self._U.data_ptr(),
+                                           self._status.data_ptr(), self._iters.data_ptr(), self._active.data_ptr(), s),
+                       "mpcqp_solve")
         return BatchSolution(self._u0[:B], self._X[:B], self._U[:B], self._status[:B], self._iters[:B],
                              self._active[:B])
 

@@ -110,15 +110,31 @@ class FleetTracker:
     are ``mpc.to_parameters(map_resolution)`` as in ``control_stage.py:73``, or ``params`` (an
     ``MPCParameters`` of the same horizon) where given: blocks an ``MPCConfig`` cannot express, such as
     a non-diagonal Q.
+
+    ``warm_start=True`` (with ``fused=True``, without classes): inside a launch each vehicle's solves
+    start from the ``U`` of its step before, shifted one step (``mpcqp_fleet_loop_warm``): one polish
+    attempt of at most ``guess_passes`` passes (default ``_lib.DEFAULT_GUESS_PASSES``) before ADMM, which
+    a hit skips; a miss runs the cold solve unchanged.  Results equal the cold loop's to rounding.
     """
+
+    warm_start = False
+    guess_passes = _lib.DEFAULT_GUESS_PASSES
 
     def __init__(self, mpc, *, map_resolution: float, max_vehicles: int, max_ref_len: int,
                  device=None, use_graph: bool = True, fused: bool = False,
-                 relaxed_settings: Optional[dict] = None, params=None, **settings) -> None:
+                 relaxed_settings: Optional[dict] = None, params=None, warm_start: bool = False,
+                 guess_passes: Optional[int] = None, **settings) -> None:
         import torch
 
         from ..control.mpc_controller import BatchedMPCController
 
+        # warm start (mpcqp_fleet_loop_warm): inside a launch every solve starts from the step before
+        if warm_start and not fused:
+            raise ValueError("warm_start needs fused=True: only the fused loop carries a guess from step to step")
+        if guess_passes is not None and not warm_start:
+            raise ValueError("guess_passes needs warm_start=True")
+        self.warm_start = bool(warm_start)
+        self.guess_passes = _lib.DEFAULT_GUESS_PASSES if guess_passes is None else int(guess_passes)
         self._torch = torch
         self.mpc = mpc
         self.params = mpc.to_parameters(map_resolution) if params is None else params
@@ -164,6 +180,8 @@ class FleetTracker:
             return
         if not self.fused:
             raise ValueError("set_classes needs fused=True: only the fused loop runs per-vehicle classes")
+        if self.warm_start:
+            raise ValueError("set_classes does not combine with warm_start: the warm loop runs one parameter block")
         if self.horizon > 32:
             raise ValueError(f"set_classes needs a horizon <= 32 (the fused loop), got {self.horizon}")
         params_list = list(params_list)
@@ -325,6 +343,10 @@ class FleetTracker:
             _lib.check(self._L.mpcqp_fleet_loop_mixed(self._nominal._ws, self._relaxed._ws, ctypes.byref(self._fleet),
                                                       self._bufs["cls"].data_ptr(), int(steps), s),
                        "mpcqp_fleet_loop_mixed")
+            return
+        if self.warm_start:  # fused, each step's solves started from the step before (cold at every launch)
+            _lib.check(self._L.mpcqp_fleet_loop_warm(self._nominal._ws, self._relaxed._ws, ctypes.byref(self._fleet),
+                                                     int(steps), self.guess_passes, s), "mpcqp_fleet_loop_warm")
             return
         if self.fused:
             _lib.check(self._L.mpcqp_fleet_loop(self._nominal._ws, self._relaxed._ws, ctypes.byref(self._fleet),

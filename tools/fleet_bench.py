@@ -116,6 +116,68 @@ def mixed_bench(a) -> None:
     print(json.dumps(out))
 
 
+def warm_bench(a) -> None:
+    """The cold fused loop (--pairing applies to it) against the warm-started one (mpcqp_fleet_loop_warm) at
+    each --guess-passes value, on the same vehicles: the sides alternate within every repeat, the order
+    rotating from repeat to repeat; the timed window holds the loop launch up to a synchronise."""
+    import torch
+
+    from mpcqp import scenarios
+    from mpcqp.config import MPCConfig
+    from mpcqp.pipeline.fleet import FleetTracker
+
+    dev = torch.device("cuda:0")
+    out = {"metric": "closed-loop vehicle-steps/s, loop launch only", "horizon": a.horizon, "sim_steps": a.steps,
+           "pairing_of_cold": a.pairing, "plan": a.plan, "reps": a.reps, "runs": []}
+    mpc = MPCConfig(horizon=a.horizon, sim_steps=a.steps)
+    for V in a.vehicles:
+        if a.plan == "config1":  # the default plan itself, every vehicle from its start
+            plan = scenarios.load_default_plan()
+            paths = [plan["path"]] * V
+            starts = np.tile(np.asarray(plan["start"], dtype=float)[:2], (V, 1))
+            goals = np.tile(np.asarray(plan["path"][-1], dtype=float)[:2], (V, 1))
+        else:
+            paths, starts, goals = scenarios.fleet5(V)
+        ref_len = 160
+        if a.plan == "config1":
+            from mpcqp.control.ref_builder import build_reference
+
+            ref_len = len(build_reference(paths[0], mpc.v_px_s, a.horizon, mpc.dt))
+        kw = dict(map_resolution=0.8, max_vehicles=V, max_ref_len=ref_len, device=dev, fused=True)
+        sides = {"cold": FleetTracker(mpc, pairing=a.pairing, **kw)}
+        for gp in a.guess_passes:
+            sides[f"warm:{gp}"] = FleetTracker(mpc, warm_start=True, guess_passes=gp, **kw)
+        names = list(sides)
+        times = {k: [] for k in names}
+        for r in range(a.reps + 1):  # repeat 0 warms up
+            for ft in sides.values():
+                ft.reset_from_plans(paths, starts, goals, device_reference=a.plan != "config1")
+            for k in names[r % len(names):] + names[:r % len(names)]:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                sides[k].step(a.steps)
+                torch.cuda.synchronize()
+                if r:
+                    times[k].append(time.perf_counter() - t0)
+        res = {k: ft.result() for k, ft in sides.items()}
+        cold = res["cold"]
+        run = {"vehicles": V, "vehicle_steps": int(cold.steps.sum()), "goal_reached": int((cold.phase == 1).sum()),
+               "aborted": int((cold.phase == 2).sum())}
+        for k in names:
+            ts, rk = times[k], res[k]
+            med = float(np.median(ts))
+            run[k] = {"seconds_median": med, "seconds_min": min(ts), "seconds_max": max(ts), "seconds": ts,
+                      "value": int(rk.steps.sum()) / med, "time_over_cold": med / float(np.median(times["cold"])),
+                      "same_steps_and_phases": bool((rk.steps == cold.steps).all() and (rk.phase == cold.phase).all()),
+                      "max_state_diff_vs_cold": max((float(np.abs(x - y).max()) for x, y in zip(rk.states, cold.states)
+                                                     if len(x) and x.shape == y.shape), default=0.0)}
+        out["runs"].append(run)
+        for ft in sides.values():
+            ft.close()
+        print(json.dumps(run), flush=True)
+    print(json.dumps(out))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--vehicles", type=int, nargs="+", default=[100, 1024, 4096])
@@ -127,9 +189,22 @@ def main() -> None:
                     help="two vehicles per wave for N <= 15 (mpcqp_set_pairing)")
     ap.add_argument("--classes", type=int, default=0,
                     help="K > 0: one mixed fused launch (mpcqp_fleet_loop_mixed) against K homogeneous fused launches")
+    ap.add_argument("--warm", action="store_true",
+                    help="the cold fused loop against the warm-started one (mpcqp_fleet_loop_warm), interleaved")
+    ap.add_argument("--guess-passes", type=int, nargs="+", default=None,
+                    help="with --warm: the attempt's pass limits to compare (default: the library's)")
+    ap.add_argument("--plan", default="fleet5", choices=["fleet5", "config1"],
+                    help="with --warm: RRT*-branch plans, or every vehicle on the default (config-1) plan")
     a = ap.parse_args()
     if a.classes:
         mixed_bench(a)
+        return
+    if a.warm:
+        if a.guess_passes is None:
+            from mpcqp import _lib
+
+            a.guess_passes = [_lib.DEFAULT_GUESS_PASSES]
+        warm_bench(a)
         return
     import torch
 
