@@ -244,6 +244,37 @@ int mpcqp_solve_staged(mpcqp_ws* ws);
  * debug builds) run mpcqp_solve_staged.  Not thread-safe per workspace (the closed loop is sequential). */
 int mpcqp_solve_served(mpcqp_ws* ws);
 
+/*
+ * The B = 1 path from a caller's guess (additive to ABI 9): mpcqp_solve_warm's contract, word for word,
+ * for the one staged QP -- the warm start of the sequential closed loop, where the previous step's U,
+ * shifted one step, is close to the optimum.
+ * mpcqp_stage_guess allocates, once, a third block owned by the workspace (pinned, device-mapped,
+ * coherent; freed by mpcqp_destroy) and returns its host address:
+ *   guess  2 x N doubles, the layout of the U output (the caller writes them in place; they may be
+ *          copied from the `out` block's U of the previous solve)
+ * It is filled with NaN, so a solve before any write is a cold one.  MPCQP_E_STATE before mpcqp_stage;
+ * NULL ws or guess: MPCQP_E_ARG.
+ * mpcqp_solve_staged_warm is mpcqp_solve_staged with that block as U_guess: one launch (k_solve_warm at
+ * B = 1) and one synchronisation.  mpcqp_solve_served_warm is mpcqp_solve_served with it: the resident
+ * wave runs k_serve_warm, which reads the guess and guess_passes of each request after it has seen the
+ * request (the host writes both before it raises the request).  Per request:
+ *   unusable  any of the 2N entries non-finite, guess_passes <= 0, or MPCQP_METHOD_NEWTON: the cold
+ *             solve; every output, iters included, is mpcqp_solve_staged's / mpcqp_solve_served's bit for bit.
+ *   hit       status MPCQP_SOLVED at the exact optimum, iters[0] == 0, iters[1..3] count the attempt.
+ *   miss      u0, X, U, status and active are the cold solve's bit for bit, iters[0] the cold value,
+ *             iters[1..3] the cold values plus the attempt's.
+ * Both return MPCQP_E_HORIZON where the parameter block does not run the one-wave kernel (N > 32,
+ * reproducible, debug_state) -- there is no silent cold fallback -- and MPCQP_E_STATE before
+ * mpcqp_stage_guess; in both cases nothing is enqueued and nothing is written.
+ * mpcqp_solve_served_warm shares every mechanism of mpcqp_solve_served: the workspace's lock, one
+ * server per device, the wave that leaves after 2 ms and is started again, the 30 s limit, and
+ * mpcqp_debug_serve_fault.  A workspace has one resident wave, of one kind: a served call of the other kind
+ * (cold after warm, warm after cold) first stops it, as a request on another workspace does.
+ * mpcqp_set_params and mpcqp_destroy stop either kind. */
+int mpcqp_stage_guess(mpcqp_ws* ws, double** guess);
+int mpcqp_solve_staged_warm(mpcqp_ws* ws, int guess_passes);
+int mpcqp_solve_served_warm(mpcqp_ws* ws, int guess_passes);
+
 /* Two QPs per wave for horizons N <= 15 (2N <= 30 variables: a one-wave QP leaves half its lanes on
  * padding): lanes 0-31 and 32-63 of a wave solve two QPs of the batch (mpcqp_solve with the model
  * built in the solve) or two vehicles of the fused loop (mpcqp_fleet_loop, mpcqp_swarm_loop), with

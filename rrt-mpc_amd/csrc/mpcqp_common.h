@@ -529,6 +529,16 @@ struct ServeLaunch {
 typedef void (*serve_t)(hipStream_t, const mpcqp_params&, const ServeLaunch&);
 // nullptr when the parameter block does not run the one-wave kernel; defined in mpcqp.hip
 serve_t server(const mpcqp_params& p);
+// The server from a caller's guess (mpcqp_solve_served_warm, k_serve_warm): k_serve's launch plus the
+// workspace's guess block (mpcqp_stage_guess): 2 x N doubles in the layout of U, and behind them the
+// request's guess_passes.  The host writes both before it raises box->req.
+struct ServeWarmLaunch {
+  ServeLaunch serve;
+  const double* guess;    // device address of the guess block
+  const int32_t* passes;  // device address of guess_passes (the block's last 8 bytes)
+};
+typedef void (*serve_warm_t)(hipStream_t, const mpcqp_params&, const ServeWarmLaunch&);
+serve_warm_t server_warm(const mpcqp_params& p);  // nullptr as server()
 typedef void (*fleet_loop_t)(hipStream_t, const mpcqp_params*, const mpcqp_fleet&, int, const LoopTrigger&);
 // the fused loop with a class per vehicle: the table of 2K interleaved blocks, cls (V indices), K, the
 // fleet, steps, the dispatch order (or nullptr)
@@ -540,7 +550,8 @@ typedef void (*fleet_loop_warm_t)(hipStream_t, const mpcqp_params*, const mpcqp_
 // templates of mpcqp_solve.h): k_solve, k_solve_mixed (a parameter block per QP), k_solve_pair (two
 // QPs per wave, fused K1; nullptr above kPairMaxHorizon), k_serve (the B = 1 server), k_fleet_loop
 // (the fused closed loop), k_fleet_loop_mixed (the same with a class per vehicle), k_solve_warm (from a
-// caller's guess) and k_fleet_loop_warm (the fused loop, each step from the one before).  The object that
+// caller's guess), k_fleet_loop_warm (the fused loop, each step from the one before) and k_serve_warm
+// (the B = 1 server from a caller's guess).  The object that
 // instantiates a horizon registers it from a namespace-scope
 // initialiser (register_horizons, mpcqp_solve.h); an all-null entry is a horizon not compiled in.
 struct HorizonKernels {
@@ -550,6 +561,7 @@ struct HorizonKernels {
   fleet_loop_mixed_t loop_mixed;
   launcher_t warm;
   fleet_loop_warm_t loop_warm;
+  serve_warm_t serve_warm;
 };
 // fills entry N of the table in mpcqp.hip (constant-initialised, so the order of the objects'
 // initialisers does not matter)
@@ -643,6 +655,10 @@ struct mpcqp_ws {
   uint8_t* stage_out = nullptr;    // host address (u0 | X | U | status | iters | active)
   uint8_t* stage_out_d = nullptr;  // its device address
   hipStream_t stage_stream = nullptr;
+  // the guess block of the warm B = 1 calls (mpcqp_stage_guess): 2 x N doubles, then guess_passes (i32)
+  double* stage_guess = nullptr;    // host address
+  double* stage_guess_d = nullptr;  // its device address
+  bool serve_warm = false;          // the kind of the live server wave: k_serve_warm (else k_serve)
   // the B = 1 server: mailbox (host / device address), sequence number, a server kernel enqueued
   void* serve_box = nullptr;
   void* serve_box_d = nullptr;

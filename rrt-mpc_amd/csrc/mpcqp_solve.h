@@ -2358,12 +2358,67 @@ __global__ __launch_bounds__(kWave, 1) void k_serve(mpcqp_params p, mpcqp::Serve
   }
 }
 
+// ServeGuessWin: the B = 1 server from a caller's guess (k_serve_warm): ServeWin exactly; a type of its
+// own for ClassWin's reason (setup_qp / finish_qp shared with k_serve changed k_serve's code generation
+// at every horizon).
+struct ServeGuessWin {
+  static constexpr bool kFleet = false;
+  int ln;
+  __device__ __forceinline__ int lane() const { return ln; }
+};
+
+// The B = 1 server from a caller's guess (mpcqp_solve_served_warm): k_serve's loop, each request through
+// solve_one's warm driver under mpcqp_solve_warm's contract.  W.guess: 2 x N doubles in the layout of the U
+// output, W.passes: the request's guess_passes; both in mapped host memory, written by the host before
+// it raises req and read here only after the acquire.  The same exits as k_serve, and no wait beside its.
+template <int N>
+__global__ __launch_bounds__(kWave, 1) void k_serve_warm(mpcqp_params p, mpcqp::ServeWarmLaunch W) {
+  __shared__ SolveLds<N> sm;
+  const mpcqp::ServeLaunch& L = W.serve;
+  const int lane = threadIdx.x;
+  uint32_t last = __builtin_amdgcn_readfirstlane(
+      __hip_atomic_load(&L.box->done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
+  for (;;) {
+    const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+    uint32_t req = last;
+    while (req == last) {
+      req = __builtin_amdgcn_readfirstlane(
+          __hip_atomic_load(&L.box->req, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
+      if (req != last) break;
+      if (__builtin_amdgcn_s_memrealtime() - t0 > L.idle_ticks) return;  // idle: leave, the host relaunches
+      __builtin_amdgcn_s_sleep(1);
+    }
+    if (req == mpcqp::kServeStop) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");  // system scope: the inputs and the guess the host wrote before req
+    int ln = lane;  // opaque per solve (ServeGuessWin)
+    asm volatile("" : "+v"(ln));
+    const int passes = __builtin_amdgcn_readfirstlane(
+        __hip_atomic_load(W.passes, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
+    const double g = ln < 2 * N ? W.guess[ln] : 0.0;  // a plain load behind the fence, as the input block's
+    const double* in = L.in;
+    uint8_t* o = L.out;
+    double Ul;
+    solve_one<N, ServeGuessWin, false, true>(p, 0, nullptr, in, in + 4, in + 4 + 4 * (N + 1), ServeGuessWin{ln}, sm,
+                                        reinterpret_cast<double*>(o + L.off[0]), reinterpret_cast<double*>(o + L.off[1]),
+                                        reinterpret_cast<double*>(o + L.off[2]), reinterpret_cast<int32_t*>(o + L.off[3]),
+                                        reinterpret_cast<int32_t*>(o + L.off[4]), o + L.off[5], Ul, Guess<true>{g, passes});
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");  // system scope: the outputs before done
+    if (lane == 0) __hip_atomic_store(&L.box->done, req, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    last = req;
+    __syncthreads();  // the next solve reuses the LDS
+  }
+}
+
 }  // namespace
 
 namespace mpcqp {
 template <int N>
 void launch_serve(hipStream_t s, const mpcqp_params& p, const ServeLaunch& L) {
   hipLaunchKernelGGL(k_serve<N>, dim3(1), dim3(kWave), 0, s, p, L);
+}
+template <int N>
+void launch_serve_warm(hipStream_t s, const mpcqp_params& p, const ServeWarmLaunch& W) {
+  hipLaunchKernelGGL(k_serve_warm<N>, dim3(1), dim3(kWave), 0, s, p, W);
 }
 template <int N>
 void launch_solve(hipStream_t s, const Launch& L) {
@@ -2416,7 +2471,8 @@ void launch_solve_pair(hipStream_t s, const Launch& L) {
 template <int LO, int HI>
 int register_horizons() {
   HorizonKernels k{&launch_solve<LO>, &launch_solve_mixed<LO>, nullptr, &launch_serve<LO>, &launch_fleet_loop<LO>,
-                   &launch_fleet_loop_mixed<LO>, &launch_solve_warm<LO>, &launch_fleet_loop_warm<LO>};
+                   &launch_fleet_loop_mixed<LO>, &launch_solve_warm<LO>, &launch_fleet_loop_warm<LO>,
+                   &launch_serve_warm<LO>};
   if constexpr (LO <= kPairMaxHorizon) k.pair = &launch_solve_pair<LO>;
   register_horizon(LO, k);
   if constexpr (LO < HI) return register_horizons<LO + 1, HI>();

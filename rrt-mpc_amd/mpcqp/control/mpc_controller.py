@@ -285,7 +285,7 @@ class BatchedMPCController:
         return BatchSolution(self._u0[:B], self._X[:B], self._U[:B], self._status[:B], self._iters[:B],
                              self._active[:B])
 
-    def solve_one(self, x0, ref, u_prev=None):
+    def solve_one(self, x0, ref, u_prev=None, *, U_guess=None, guess_passes=None):
         """One QP for the sequential closed loop of ``TrajectoryTracker.track``, where host overhead
         dominates a B=1 step.  The workspace's own blocks of pinned, device-mapped host memory hold
         the inputs and outputs, which the kernels read and write in place (``mpcqp_stage`` /
@@ -293,18 +293,41 @@ class BatchedMPCController:
         library call hands the QP to the workspace's resident solver wave (started by the first
         call, gone after 2 ms idle) and waits for its answer -- no kernel launch per step.
         ``x0`` (4,), ``ref`` (>= N+1, 4) -- rows 0..N are used --, ``u_prev`` (2,) host arrays.
-        Returns host numpy ``(status, u0, X, U)``; X (4, N+1) and U (2, N) are fresh arrays.
-        A fault that surfaces at the synchronisation raises ``_lib.DeviceError``."""
+        Returns host numpy ``(status, u0, X, U)``; X (4, N+1) and U (2, N) are fresh arrays;
+        ``last_iters`` holds a copy of the solve's four counters.
+        A fault that surfaces at the synchronisation raises ``_lib.DeviceError``.
+
+        ``U_guess`` (2, N), the layout of ``U``: warm start under ``mpcqp_solve_warm``'s contract
+        (``mpcqp_solve_served_warm`` / ``mpcqp_solve_staged_warm``): the guess is written into the
+        workspace's guess block and the QP first gets one polish attempt of at most ``guess_passes``
+        passes (default ``_lib.DEFAULT_GUESS_PASSES``) from it; a hit has ``last_iters[0] == 0``, a miss
+        or an unusable guess runs the cold solve unchanged.  Horizons <= 32 in fast mode; others raise
+        ``_lib.LibraryError``.  Without ``U_guess`` the call is the cold one exactly."""
+        if U_guess is None and guess_passes is not None:
+            raise ValueError("solve_one(guess_passes=...) needs U_guess")
         io = self._one
         if io is None:
             io = self._one = self._stage()
+        solve1 = self._solve1
+        if U_guess is not None:
+            g = np.asarray(U_guess, dtype=float)
+            if g.shape != (2, self.horizon):
+                raise ValueError(f"U_guess must have shape (2, {self.horizon}), got {g.shape}")
+            warm1 = self._solve1_warm
+            if warm1 is None:
+                raise _lib.LibraryError("this libmpcqp build has no warm B = 1 calls (mpcqp_solve_served_warm)")
+            if "guess" not in io:
+                io["guess"] = self._stage_guess()
+            io["guess"][:] = g
+            passes = _lib.DEFAULT_GUESS_PASSES if guess_passes is None else int(guess_passes)
+            solve1 = lambda ws: warm1(ws, passes)  # noqa: E731
         io["x0"][:] = x0
         io["ref"][:] = ref[: self.horizon + 1]
         if u_prev is None:
             io["up"][:] = 0.0
         else:
             io["up"][:] = u_prev
-        rc = self._solve1(self._ws)
+        rc = solve1(self._ws)
         if rc != 0:
             msg = self._L.mpcqp_last_error().decode(errors="replace")
             if rc == _lib.E_DEVICE:
@@ -314,14 +337,35 @@ class BatchedMPCController:
 
     _one = None
 
+    @property
+    def last_iters(self):
+        """A copy of the four counters of the last ``solve_one`` (ADMM iterations, polish passes,
+        factorizations, line-search trials), read from the output block when asked for: the cold call pays
+        nothing for it.  None before the first solve."""
+        io = self._one
+        return None if io is None else io["iters"].copy()
+
+    def _stage_guess(self):
+        """numpy view (2, N) of the workspace's guess block (mpcqp_stage_guess: NaN until written)."""
+        hg = ctypes.c_void_p()
+        with self._torch.cuda.device(self.device):
+            rc = self._L.mpcqp_stage_guess(self._ws, ctypes.byref(hg))
+        if rc != 0:
+            raise _lib.DeviceError(f"mpcqp_stage_guess failed ({rc}): "
+                                   f"{self._L.mpcqp_last_error().decode(errors='replace')}")
+        N = self.horizon
+        return np.frombuffer((ctypes.c_double * (2 * N)).from_address(hg.value), np.float64).reshape(2, N)
+
     def _stage(self) -> dict:
         """numpy views of the workspace's B=1 staging blocks (allocated by the first mpcqp_stage;
         an allocation failure raises DeviceError)."""
         N = self.horizon
         # the resident B=1 server (mpcqp_solve_served: no launch per call) unless MPCQP_B1_SERVER=0
         # asks for a launch per call (mpcqp_solve_staged)
-        self._solve1 = (self._L.mpcqp_solve_staged if os.environ.get("MPCQP_B1_SERVER", "1") == "0"
-                        else self._L.mpcqp_solve_served)
+        launched = os.environ.get("MPCQP_B1_SERVER", "1") == "0"
+        self._solve1 = self._L.mpcqp_solve_staged if launched else self._L.mpcqp_solve_served
+        # (None: an older library loaded under MPCQP_ABI_ANY has no warm B = 1 calls; solve_one(U_guess=...) raises)
+        self._solve1_warm = getattr(self._L, "mpcqp_solve_staged_warm" if launched else "mpcqp_solve_served_warm", None)
         hin, hout = ctypes.c_void_p(), ctypes.c_void_p()
         offs = (ctypes.c_int32 * 6)()
         with self._torch.cuda.device(self.device):
@@ -407,11 +451,21 @@ def _single_controller(params, method: str = "admm", **settings) -> BatchedMPCCo
 class MPCController:
     """Quadratic-cost MPC controller with soft bounds and rate limits (``mpc_controller.py:33-145``)."""
 
-    def __init__(self, params: MPCParameters, **settings) -> None:
+    def __init__(self, params: MPCParameters, warm_start: bool = False, guess_passes: Optional[int] = None,
+                 **settings) -> None:
         # ``settings``: optional solver settings of ``mpcqp_params`` (rho, max_iter, polish, ...);
         # the reference's constructor takes ``params`` alone and so does every caller of it.
+        # ``warm_start``: ``solve(..., u_init=G)`` starts from G ((N, 2), the reference's layout) with one
+        # polish attempt of at most ``guess_passes`` passes (``BatchedMPCController.solve_one``); neither
+        # is a solver setting, and neither reaches the controller cache's key.
+        if warm_start and int(params.horizon) > _lib.WIDE_MIN_HORIZON - 1:
+            raise ValueError(f"warm_start needs horizon <= {_lib.WIDE_MIN_HORIZON - 1} (the one-wave kernel), "
+                             f"got {int(params.horizon)}")
         self._params = params
         self._settings = dict(settings)
+        self.warm_start = bool(warm_start)
+        self.guess_passes = guess_passes
+        self.last_iters = None  # the four counters of the last solve (None: it never reached the device)
 
     def solve(
         self,
@@ -421,8 +475,16 @@ class MPCController:
         u_init: Optional[FloatArray] = None,
         u_prev: Optional[FloatArray] = None,
     ) -> Tuple[Optional[FloatArray], Optional[FloatArray], Optional[FloatArray]]:
-        # u_init is accepted and ignored, as in the reference (mpc_controller.py:50-51).
+        # u_init is accepted and ignored, as in the reference (mpc_controller.py:50-51), unless the
+        # controller was made with warm_start: then it is the guess, (N, 2) as the reference lays it out.
         N = int(self._params.horizon)
+        warm = {}
+        if self.warm_start and u_init is not None:
+            g = np.asarray(u_init, dtype=float)
+            if g.shape != (N, 2):
+                raise ValueError(f"u_init must have shape ({N}, 2), got {g.shape}")
+            warm = dict(U_guess=np.ascontiguousarray(g.T), guess_passes=self.guess_passes)
+        self.last_iters = None
         x0 = np.asarray(x0, dtype=float)
         ref = np.asarray(ref_traj, dtype=float)
         # The reference reads rows 0..N of ref_traj (mpc_controller.py:68,111) after unwrapping
@@ -442,7 +504,8 @@ class MPCController:
             settings = {**settings, "scaling": OSQP_SCALING}
         ctrl = _single_controller(self._params, **settings)
         try:
-            status, _, X, U = ctrl.solve_one(x0, ref, up)
+            status, _, X, U = ctrl.solve_one(x0, ref, up, **warm)
+            self.last_iters = getattr(ctrl, "last_iters", None)
         except _lib.LibraryError:
             # ... while a refused or failed launch of the solve maps to (None, None, None), as the
             # reference maps cp.SolverError (mpc_controller.py:133-135).  A fault that surfaces at
@@ -457,7 +520,8 @@ class MPCController:
             # the exact optimum; it needs a max_iter far below the reference's 60000.)
             ctrl = _single_controller(self._params, **{**settings, "scaling": OSQP_SCALING})
             try:
-                status, _, X, U = ctrl.solve_one(x0, ref, up)
+                status, _, X, U = ctrl.solve_one(x0, ref, up, **warm)
+                self.last_iters = getattr(ctrl, "last_iters", None)
             except _lib.LibraryError:
                 LOG.exception("GPU failed during MPC solve")
                 return None, None, None

@@ -15,6 +15,7 @@ from typing import Any, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .. import _lib
 from ..control.mpc_controller import MPCController, MPCParameters
 from ..control.ref_builder import build_reference
 from ..control.vehicle_model import f_discrete
@@ -77,8 +78,33 @@ class TrajectoryTracker:
     # reference constructs TrajectoryTracker(mpc, viz) and gets the library defaults.
     solver_settings: dict = field(default_factory=dict)
     relaxed_solver_settings: dict = field(default_factory=dict)
+    # Warm start (off by default; no counterpart in the reference): each step's solves start from the U
+    # of the last accepted solve, shifted one step with its last column repeated, as one polish attempt
+    # of at most ``guess_passes`` passes (``_lib.DEFAULT_GUESS_PASSES`` when None) before ADMM
+    # (``MPCController(warm_start=True)``; horizons <= 32).  A hit returns the exact optimum without an
+    # ADMM iteration, a miss the cold solve's answer: the closed loop is the same to rounding.
+    warm_start: bool = False
+    guess_passes: Optional[int] = None
     # parameters of the last track() call; step() without params solves with them
     _params: Optional[MPCParameters] = field(default=None, init=False, repr=False, compare=False)
+    # warm start: the U (2, N) of the last accepted solve (None: the next step solves cold), the solves
+    # that were handed a guess, and those of them that hit (solved with no ADMM iteration)
+    _carried_U: Optional[np.ndarray] = field(default=None, init=False, repr=False, compare=False)
+    warm_attempts: int = field(default=0, init=False, compare=False)
+    warm_hits: int = field(default=0, init=False, compare=False)
+
+    def _warm_solve(self, params, settings, state, reference, u_prev, u_init):
+        """One solve of ``_solve_with_relaxation``; with ``u_init`` (warm start only) from that guess."""
+        if not self.warm_start:
+            return MPCController(params, **settings).solve(state, reference, u_prev=u_prev)
+        passes = _lib.DEFAULT_GUESS_PASSES if self.guess_passes is None else self.guess_passes
+        controller = MPCController(params, warm_start=True, guess_passes=passes, **settings)
+        out = controller.solve(state, reference, u_init=u_init, u_prev=u_prev)
+        if u_init is not None:
+            self.warm_attempts += 1
+            it = controller.last_iters
+            self.warm_hits += int(out[0] is not None and it is not None and int(it[0]) == 0)
+        return out
 
     def _solve_with_relaxation(
         self,
@@ -86,10 +112,11 @@ class TrajectoryTracker:
         reference: np.ndarray,
         u_prev: np.ndarray,
         base_params: MPCParameters,
+        u_init: Optional[np.ndarray] = None,
     ) -> Tuple[Optional[np.ndarray], Optional[np.ndarray], Optional[np.ndarray]]:
-        """``control_stage.py:33-56``: nominal solve, then one retry with relaxed rates and speed."""
-        controller = MPCController(base_params, **self.solver_settings)
-        u0, Xp, Up = controller.solve(state, reference, u_prev=u_prev)
+        """``control_stage.py:33-56``: nominal solve, then one retry with relaxed rates and speed.
+        ``u_init`` ((N, 2); warm start only): the guess both solves start from."""
+        u0, Xp, Up = self._warm_solve(base_params, self.solver_settings, state, reference, u_prev, u_init)
         if u0 is not None:
             return u0, Xp, Up
         LOG.warning("MPC infeasible; applying rate relaxation and speed reduction")
@@ -102,8 +129,8 @@ class TrajectoryTracker:
                 (base_params.du_bounds[1][0] - 0.05, base_params.du_bounds[1][1] + 0.05),
             ),
         )
-        return MPCController(relaxed_params, **self.relaxed_solver_settings).solve(
-            state, relaxed_reference, u_prev=u_prev)
+        return self._warm_solve(relaxed_params, self.relaxed_solver_settings, state, relaxed_reference, u_prev,
+                                u_init)
 
     def step(
         self,
@@ -133,7 +160,16 @@ class TrajectoryTracker:
                 LOG.warning("step() before any track() and without params or map_resolution: assuming "
                             "map_resolution=%s (MapConfig's default) for the px/m scaling", DEFAULT_MAP_RESOLUTION)
                 params = self._params = self.mpc.to_parameters(DEFAULT_MAP_RESOLUTION)
-        u0, Xp, _ = self._solve_with_relaxation(state, ref_window, u_prev, params)
+        if not self.warm_start:
+            u0, Xp, _ = self._solve_with_relaxation(state, ref_window, u_prev, params)
+        else:
+            # the last accepted U one step on, its last column repeated (N = 1 has nothing to shift),
+            # in the reference's u_init layout (N, 2)
+            U = self._carried_U
+            guess = None if U is None else np.concatenate([U[:, 1:], U[:, -1:]], axis=1).T
+            u0, Xp, Up = self._solve_with_relaxation(state, ref_window, u_prev, params, guess)
+            ok = u0 is not None and Xp is not None and Up is not None
+            self._carried_U = np.array(Up, dtype=float, copy=True) if ok else None
         if u0 is None or Xp is None:
             return None, None, None
         next_state = f_discrete(np.asarray(state, dtype=float), u0, params.dt, params.wheelbase_px)
@@ -157,6 +193,7 @@ class TrajectoryTracker:
             raise RuntimeError("Planner returned an empty path")
 
         base_params = self._params = self.mpc.to_parameters(map_resolution)
+        self._carried_U = None  # a new run: its first step solves cold
         horizon = base_params.horizon
         wheelbase_px = base_params.wheelbase_px
 

@@ -14,6 +14,19 @@ own 65 windows of closed_loop.npz, cycled):
                       mpcqp_solve + torch.cuda.synchronize (no mapped memory);
   * kernel_event_us   HIP events around the device-input solve (the kernel alone, on its stream);
   * track_ms_per_step the whole drop-in TrajectoryTracker.track loop (bench.py's config1 figure).
+
+    python tools/b1_latency.py --warm [--horizons 10 15 20] [--reps 5] > profiles/served_warm/<name>.json
+
+The warm start of the B = 1 path against the cold path of the same process, interleaved (cold block,
+warm block, cold block, ...), each figure the median of `reps` repeats, per horizon on the config-1 plan's
+own closed loop (its windows, and as the guess of window k the U of window k - 1 shifted one step):
+  * solve_one_us       BatchedMPCController.solve_one per window: the served call with its input writes,
+                       cold and with U_guess (which adds the guess write and the warm served call);
+  * kernel_event_us    HIP events around mpcqp_build + mpcqp_solve / mpcqp_solve_warm of the same QPs from
+                       device memory (k_solve<N> / k_solve_warm<N> at B = 1: the solve alone);
+  * track_ms_per_step  TrajectoryTracker.track, cold and with warm_start=True;
+  * hit_rate           solves from a guess that ended without an ADMM iteration (iters[0] == 0);
+  * guess_write_us     the host's share: shifting the previous U and writing it into the guess block.
 """
 from __future__ import annotations
 
@@ -42,11 +55,147 @@ def best_of(fn, calls: int, reps: int = 5) -> float:
     return best
 
 
+def _median_blocks(fns: dict, reps: int) -> tuple:
+    """(name -> median over `reps` of fn() (a time), name -> every repeat), the functions taking turns
+    within each repeat"""
+    got = {name: [] for name in fns}
+    for _ in range(reps):
+        for name, fn in fns.items():
+            got[name].append(fn())
+    return {name: float(np.median(v)) for name, v in got.items()}, got
+
+
+def warm_horizon(N: int, reps: int) -> dict:
+    """The cold and the warm B = 1 path at horizon N on the config-1 plan (see the module docstring)."""
+    import torch
+
+    from mpcqp import _lib, scenarios
+    from mpcqp.config import MPCConfig, VizConfig
+    from mpcqp.control.mpc_controller import _single_controller
+    from mpcqp.control.vehicle_model import f_discrete
+    from mpcqp.control.ref_builder import build_reference
+    from mpcqp.pipeline.control_stage import TrajectoryTracker, window_at
+
+    plan = scenarios.load_default_plan()
+    path = [tuple(map(float, q)) for q in plan["path"]]
+    planning = SimpleNamespace(plan=SimpleNamespace(success=True, path=path))
+    maps = SimpleNamespace(start=tuple(plan["start"]), goal=tuple(plan["goal"]))
+    mpc = MPCConfig(horizon=N, sim_steps=300)
+    params = mpc.to_parameters(0.8)
+    ctrl = _single_controller(params)
+    L = _lib.lib()
+
+    # the loop's own windows and optima (TrajectoryTracker.track's loop, cold)
+    state = np.array([maps.start[0], maps.start[1], np.arctan2(path[1][1] - path[0][1], path[1][0] - path[0][0]), 5.0])
+    u_prev, path_idx = np.zeros(2), 0
+    ref_global = build_reference(path, mpc.v_px_s, N, mpc.dt)
+    x0s, wins, ups, Us = [], [], [], []
+    for _ in range(mpc.sim_steps):
+        w = window_at(ref_global, path_idx, N)
+        st, u0, X, U = ctrl.solve_one(state, w, u_prev)
+        if st != _lib.SOLVED:
+            raise SystemExit(f"N={N}: status {st} on the plan's own loop")
+        x0s.append(state.copy()), wins.append(w.copy()), ups.append(u_prev.copy()), Us.append(U)
+        state = f_discrete(state, u0, params.dt, params.wheelbase_px)
+        u_prev = u0.copy()
+        if path_idx < len(ref_global) - 2 and np.sum((state[:2] - ref_global[path_idx][:2]) ** 2) > 25.0:
+            path_idx += 1
+        if np.hypot(state[0] - maps.goal[0], state[1] - maps.goal[1]) < 8.0:
+            break
+    n = len(x0s)
+    guesses = [None] + [np.concatenate([Us[k - 1][:, 1:], Us[k - 1][:, -1:]], axis=1) for k in range(1, n)]
+    out = {"horizon": N, "windows": n, "reps": reps, "guess_passes": _lib.DEFAULT_GUESS_PASSES,
+           "settings": dict(ctrl.settings)}
+
+    def served(warm):
+        def block():
+            kw = lambda k: dict(U_guess=guesses[k]) if warm else {}  # noqa: E731
+            ctrl.solve_one(x0s[1], wins[1], ups[1], **kw(1))  # the wave of this kind is resident
+            t0 = time.perf_counter()
+            for k in range(1, n):
+                ctrl.solve_one(x0s[k], wins[k], ups[k], **kw(k))
+            return (time.perf_counter() - t0) / (n - 1) * 1e6
+        return block
+
+    med, runs = _median_blocks({"cold": served(False), "warm": served(True)}, reps)
+    out["solve_one_us"] = {**med, "runs": runs}
+    hits = 0
+    for k in range(1, n):
+        ctrl.solve_one(x0s[k], wins[k], ups[k], U_guess=guesses[k])
+        hits += int(ctrl.last_iters[0] == 0)
+    out["hit_rate"] = {"hits": hits, "attempts": n - 1}
+
+    # the host's share of a warm call: the shift and the write into the mapped block
+    block = ctrl._one["guess"]
+
+    def guess_write():
+        t0 = time.perf_counter()
+        for k in range(1, n):
+            U = Us[k - 1]
+            block[:] = np.asarray(np.concatenate([U[:, 1:], U[:, -1:]], axis=1), dtype=float)
+        return (time.perf_counter() - t0) / (n - 1) * 1e6
+
+    out["guess_write_us"] = _median_blocks({"shift_and_write": guess_write}, reps)[0]["shift_and_write"]
+
+    # the kernels alone: the same QPs from device memory, HIP events around build + solve
+    dev = torch.device("cuda:0")
+    x0_t, w_t, up_t = (torch.from_numpy(np.stack(v)).to(dev) for v in (x0s, wins, ups))
+    g_t = torch.from_numpy(np.stack([Us[0]] + guesses[1:])).to(dev)
+    stream = torch.cuda.current_stream(dev)
+    s = ctypes.c_void_p(stream.cuda_stream)
+    outs = [t.data_ptr() for t in (ctrl._u0, ctrl._X, ctrl._U, ctrl._status, ctrl._iters, ctrl._active)]
+
+    def kernel(warm):
+        def block():
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
+            for q in range(1, n):
+                ev[q][0].record(stream)
+                _lib.check(L.mpcqp_build(ctrl._ws, 1, x0_t[q].data_ptr(), w_t[q].data_ptr(), up_t[q].data_ptr(), s),
+                           "build")
+                if warm:
+                    _lib.check(L.mpcqp_solve_warm(ctrl._ws, 1, g_t[q].data_ptr(), _lib.DEFAULT_GUESS_PASSES, *outs, s),
+                               "solve_warm")
+                else:
+                    _lib.check(L.mpcqp_solve(ctrl._ws, 1, *outs, s), "solve")
+                ev[q][1].record(stream)
+                torch.cuda.synchronize(dev)
+            return float(np.mean([e0.elapsed_time(e1) * 1e3 for e0, e1 in ev[1:]]))
+        return block
+
+    med, runs = _median_blocks({"cold": kernel(False), "warm": kernel(True)}, reps)
+    out["kernel_event_us"] = {**med, "runs": runs}
+
+    trackers = {"cold": TrajectoryTracker(mpc, VizConfig()), "warm": TrajectoryTracker(mpc, VizConfig(), warm_start=True)}
+
+    def track(name):
+        def block():
+            t0 = time.perf_counter()
+            st = trackers[name].track(planning, maps, map_resolution=0.8, visualize=False).states
+            return 1e3 * (time.perf_counter() - t0) / len(st)
+        return block
+
+    for name in trackers:
+        track(name)()
+    t = trackers["warm"]
+    out["track_hit_rate"] = {"hits": t.warm_hits, "attempts": t.warm_attempts}
+    med, runs = _median_blocks({name: track(name) for name in trackers}, reps)
+    out["track_ms_per_step"] = {**med, "runs": runs}
+    return out
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--horizon", type=int, default=10)
     ap.add_argument("--calls", type=int, default=400)
+    ap.add_argument("--warm", action="store_true", help="the warm start against the cold path, interleaved")
+    ap.add_argument("--horizons", type=int, nargs="+", default=[10, 15, 20], help="with --warm")
+    ap.add_argument("--reps", type=int, default=5, help="with --warm: repeats per figure (medians; at least 5)")
     a = ap.parse_args()
+    if a.warm:
+        if a.reps < 5:
+            raise SystemExit("--reps must be at least 5")
+        print(json.dumps({"warm": [warm_horizon(N, a.reps) for N in a.horizons]}, indent=1))
+        return
     import torch
 
     from mpcqp import _lib, scenarios
