@@ -175,6 +175,36 @@ __device__ __forceinline__ double wave_max(double v) {  // v >= 0
   v = max_nc(v, dpp_rows<kRowBcast31, 0xc>(v));
   return readlane(v, 63);
 }
+// one step of four max reductions at once (values >= 0, or quiet NaNs, which v_max_f64 drops against a
+// number as fmax does): the four moves, then the four maxima, so each reduction's DPP moves and their
+// wait states issue under the other three's
+#define MPCQP_MAX4_STEP(MOVE)                                             \
+  {                                                                       \
+    const double ta = MOVE(a), tb = MOVE(b), tc = MOVE(c), td = MOVE(d); \
+    a = max_nc(a, ta);                                                    \
+    b = max_nc(b, tb);                                                    \
+    c = max_nc(c, tc);                                                    \
+    d = max_nc(d, td);                                                    \
+  }
+// the steps of wave_max within the 16-lane rows and from row 0 / 2 into row 1 / 3: lanes 31 and 63 hold
+// the maxima of their 32-lane halves
+__device__ __forceinline__ void half_max4_steps(double& a, double& b, double& c, double& d) {
+  MPCQP_MAX4_STEP(dpp<kRowShr1>)
+  MPCQP_MAX4_STEP(dpp<kRowShr2>)
+  MPCQP_MAX4_STEP(dpp<kRowShr4>)
+  MPCQP_MAX4_STEP(dpp<kRowShr8>)
+  MPCQP_MAX4_STEP((dpp_rows<kRowBcast15, 0xa>))
+}
+// four wave maxima at once (max is exact and order-free: each is wave_max's value)
+__device__ __forceinline__ void wave_max4(double& a, double& b, double& c, double& d) {
+  half_max4_steps(a, b, c, d);
+  MPCQP_MAX4_STEP((dpp_rows<kRowBcast31, 0xc>))
+  a = readlane(a, 63);
+  b = readlane(b, 63);
+  c = readlane(c, 63);
+  d = readlane(d, 63);
+}
+#undef MPCQP_MAX4_STEP
 // lane i <- lane i-2 (0 for i < 2);  lane i <- lane i+2 (0 past the wave)
 __device__ __forceinline__ double shr2(double v) { return dpp<kWaveShr1>(dpp<kWaveShr1>(v)); }
 __device__ __forceinline__ double shl2(double v) { return dpp<kWaveShl1>(dpp<kWaveShl1>(v)); }
@@ -262,6 +292,7 @@ struct Lanes<false> {
   __device__ __forceinline__ static double sum(double v) { return wave_sum(v); }
   __device__ __forceinline__ static void sum2(double& a, double& b) { wave_sum2(a, b); }
   __device__ __forceinline__ static double max(double v) { return wave_max(v); }
+  __device__ __forceinline__ static void max4(double& a, double& b, double& c, double& d) { wave_max4(a, b, c, d); }
   __device__ __forceinline__ static bool any(bool b) { return wave_any(b); }
   __device__ __forceinline__ static uint64_t ballot(bool b) { return __ballot(b); }
   __device__ __forceinline__ static double shr2(double v) { return ::shr2(v); }
@@ -330,6 +361,13 @@ struct Lanes<true> {
     v = max_nc(v, dpp<kRowShr8>(v));
     v = max_nc(v, dpp_rows<kRowBcast15, 0xa>(v));
     return read<31>(v);
+  }
+  __device__ __forceinline__ static void max4(double& a, double& b, double& c, double& d) {  // >= 0 or quiet NaN
+    half_max4_steps(a, b, c, d);
+    a = read<31>(a);
+    b = read<31>(b);
+    c = read<31>(c);
+    d = read<31>(d);
   }
   __device__ __forceinline__ static uint64_t ballot(bool b) {
     const uint64_t m = __ballot(b);

@@ -97,9 +97,13 @@ struct Ctx {
   bool act, even;
   double dt;
   double D, qv;
-  double E[3], lo[3], hi[3], wb[3];
+  // the row and cost scalings' reciprocals, as the termination check multiplies by them (1.0 / x, once
+  // per QP): iE[r] = 1 / E[r] (exactly 0 where the lane has no row r, E[r] <= 0), icscale = 1 / cscale.
+  // E and cscale themselves are setup's alone, so these take their registers; 1 / D would be two more,
+  // which the horizons at the register limit do not have (scratch in k_solve<30>): the check divides.
+  double iE[3], lo[3], hi[3], wb[3];
   double c0, c10, c11, c20, c21, c22;  // Cbar's coefficients (see above)
-  double cscale;
+  double icscale;
   static constexpr int kPS = SolveSmem<N>::kPS;  // Pbar row stride
   double* __restrict__ P;  // Pbar (LDS, row-major n x n, row stride kPS)
   double* __restrict__ colb;  // SolveLds::col: the sweep's pivot-column broadcast buffers
@@ -128,7 +132,7 @@ struct Ctx {
   // masks) out of the loops and the kernel drops to one wave per SIMD.
   __device__ __forceinline__ void opaque() {
     asm volatile("" : "+v"(D), "+v"(qv), "+v"(lane));
-    asm volatile("" : "+v"(E[0]), "+v"(E[1]), "+v"(E[2]));
+    asm volatile("" : "+v"(iE[0]), "+v"(iE[1]), "+v"(iE[2]));
     asm volatile("" : "+v"(c0), "+v"(c10), "+v"(c11), "+v"(c20), "+v"(c21), "+v"(c22));
     asm volatile("" : "+v"(lo[0]), "+v"(lo[1]), "+v"(lo[2]));
     asm volatile("" : "+v"(hi[0]), "+v"(hi[1]), "+v"(hi[2]));
@@ -1101,7 +1105,7 @@ __device__ __forceinline__ bool setup_qp(const mpcqp_params& p, int b, const dou
   C.colb = lds.col;
   C.qv = qv;
   C.D = D;
-  C.cscale = cscale;
+  C.icscale = 1.0 / cscale;
   {  // Cbar's coefficients: row scaling x row coefficient x the column scaling of the variable
     const double Dm1 = LN::shr1(D), Dm2 = LN::shr1(Dm1);
     C.c0 = E[0] * D;
@@ -1113,7 +1117,7 @@ __device__ __forceinline__ bool setup_qp(const mpcqp_params& p, int b, const dou
   }
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
-    C.E[r] = E[r];
+    C.iE[r] = E[r] > 0.0 ? 1.0 / E[r] : 0.0;
     C.lo[r] = lo[r];
     C.hi[r] = hi[r];
     C.wb[r] = wb[r];
@@ -1448,44 +1452,46 @@ __device__ __forceinline__ int admm_run(const mpcqp_params& p, Ctx<N, Pair>& C, 
         const double x = S.x;
         double Ax[3];
         C.Cmul(x, Ax);
+        // Straight-line on locals, selects at the end (conditionals around the products compile to
+        // nests of exec-masked branches).  A lane without row r has iE[r] = 0: its unscaled residuals
+        // (the products with iE) are exact zeros (or NaNs, which fmax drops: the iterate itself is
+        // tested below), as neutral among the non-negative terms as leaving the row out, and its
+        // scaled ones are selected away.
         double pr = 0, nprim = 0, spr = 0, snprim = 0;
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
-          if (C.E[r] > 0.0) {
-            const double ie = 1.0 / C.E[r];
-            pr = fmax(pr, fabs((Ax[r] - S.z[r]) * ie));
-            nprim = fmax(nprim, fmax(fabs(Ax[r] * ie), fabs(S.z[r] * ie)));
-            spr = fmax(spr, fabs(Ax[r] - S.z[r]));
-            snprim = fmax(snprim, fmax(fabs(Ax[r]), fabs(S.z[r])));
-          }
+          const double ie = C.iE[r];
+          const double rz = Ax[r] - S.z[r];
+          const double t_pr = fabs(rz * ie);
+          const double t_np = fmax(fabs(Ax[r] * ie), fabs(S.z[r] * ie));
+          const double t_spr = fabs(rz);
+          const double t_snp = fmax(fabs(Ax[r]), fabs(S.z[r]));
+          const bool row = ie > 0.0;
+          pr = fmax(pr, t_pr);
+          nprim = fmax(nprim, t_np);
+          spr = fmax(spr, row ? t_spr : 0.0);
+          snprim = fmax(snprim, row ? t_snp : 0.0);
         }
-        pr = LN::max(pr);
-        nprim = LN::max(nprim);
-        spr = LN::max(spr);
-        snprim = LN::max(snprim);
+        LN::max4(pr, nprim, spr, snprim);
         const double Px = C.Pmul(x);
         const double Aty = C.CTmul(S.y);
-        double du = 0, ndual = 0, sdu = 0, sndual = 0;
-        if (act) {
-          const double id = 1.0 / C.D;
-          const double rd = Px + C.qv + Aty;
-          du = fabs(rd * id);
-          ndual = fmax(fmax(fabs(Px * id), fabs(Aty * id)), fabs(C.qv * id));
-          sdu = fabs(rd);
-          sndual = fmax(fmax(fabs(Px), fabs(Aty)), fabs(C.qv));
-        }
-        du = LN::max(du);
-        ndual = LN::max(ndual);
-        sdu = LN::max(sdu);
-        sndual = LN::max(sndual);
-        const double ic = 1.0 / C.cscale;
+        // the same past the variables: 1 / D reads as 0 there
+        const double id = act ? 1.0 / C.D : 0.0;
+        const double rd = Px + C.qv + Aty;
+        double du = fabs(rd * id);
+        double ndual = fmax(fmax(fabs(Px * id), fabs(Aty * id)), fabs(C.qv * id));
+        double sdu = act ? fabs(rd) : 0.0;
+        double sndual = act ? fmax(fmax(fabs(Px), fabs(Aty)), fabs(C.qv)) : 0.0;
+        LN::max4(du, ndual, sdu, sndual);
+        const double ic = C.icscale;
         du *= ic;
         const double ep = p.eps_abs + p.eps_rel * nprim;
         const double ed = p.eps_abs + p.eps_rel * ndual * ic;
         T.end(3);
-        // fmax drops NaNs, so test the iterate itself
-        if (LN::any(!isfinite(x) || !isfinite(S.z[0] + S.z[1] + S.z[2]) || !isfinite(S.y[0] + S.y[1] + S.y[2])) ||
-            !isfinite(pr) || !isfinite(du)) {
+        // fmax drops NaNs, so test the iterate itself (three tests in a row: with a short circuit they
+        // compile to a nest of exec-masked branches)
+        const bool fin = isfinite(x) & isfinite(S.z[0] + S.z[1] + S.z[2]) & isfinite(S.y[0] + S.y[1] + S.y[2]);
+        if (LN::any(!fin) || !isfinite(pr) || !isfinite(du)) {
           ev = kAdmmBad;
           done = true;
           break;
