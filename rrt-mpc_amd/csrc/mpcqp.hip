@@ -167,9 +167,7 @@ bool wide_solve(const mpcqp_params& p) { return p.horizon >= MPCQP_WIDE_MIN_HORI
 void register_horizon(int N, const HorizonKernels& k) {
   if (N >= 1 && N < MPCQP_WIDE_MIN_HORIZON) g_kernels[N] = k;
 }
-// the one-wave kernels of the parameter block's horizon; nullptr when it runs another kernel family
-// (long horizons, reproducible mode) or, for the entry points that keep no debug state, with debug_state
-static const HorizonKernels* one_wave(const mpcqp_params& p, bool debug_ok) {
+const HorizonKernels* one_wave(const mpcqp_params& p, bool debug_ok) {
   if (wide_solve(p) || (p.debug_state && !debug_ok) || p.horizon < 1) return nullptr;
   return &g_kernels[p.horizon];
 }
@@ -198,37 +196,17 @@ int ensure_buffers(mpcqp_ws* ws, bool model, bool state, hipStream_t s) {
   if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("hipMalloc (workspace buffers): ") + hipGetErrorString(e));
   return MPCQP_OK;
 }
-serve_t server(const mpcqp_params& p) {
-  const HorizonKernels* k = one_wave(p, false);
-  return k ? k->serve : nullptr;
-}
-serve_warm_t server_warm(const mpcqp_params& p) {
-  const HorizonKernels* k = one_wave(p, false);
-  return k ? k->serve_warm : nullptr;
-}
 bool use_pairs(const mpcqp_ws* ws, int count) {
   // a mixed build (mpcqp_build_mixed) never pairs: the two halves of a wave would need two parameter
   // blocks, which turns every parameter into a per-lane value
   if (ws->build.cls) return false;
-  const HorizonKernels* k = one_wave(ws->p, false);
+  const HorizonKernels* k = one_wave(ws->p);
   if (!k || !k->pair) return false;
   if (ws->pairing == MPCQP_PAIR_ON) return true;
   if (ws->pairing == MPCQP_PAIR_OFF) return false;
   // auto: once the QPs outnumber the wave slots (2 per SIMD): below that every QP has a wave of its
   // own, and pairing would only make each wave wait for the slower of its two QPs
   return ws->cus > 0 && count > 8 * ws->cus;
-}
-fleet_loop_t fleet_looper(const mpcqp_params& p) {
-  const HorizonKernels* k = one_wave(p, false);
-  return k ? k->loop : nullptr;
-}
-fleet_loop_mixed_t fleet_looper_mixed(const mpcqp_params& p) {
-  const HorizonKernels* k = one_wave(p, false);
-  return k ? k->loop_mixed : nullptr;
-}
-fleet_loop_warm_t fleet_looper_warm(const mpcqp_params& p) {
-  const HorizonKernels* k = one_wave(p, false);
-  return k ? k->loop_warm : nullptr;
 }
 }  // namespace mpcqp
 
@@ -345,10 +323,10 @@ void mpcqp_destroy(mpcqp_ws* ws) {
   (void)hipFree(ws->dorder);
   (void)hipFree(ws->dclasses);
   (void)hipFree(ws->dloop_classes);
-  if (ws->serve_box) (void)hipHostFree(ws->serve_box);
-  if (ws->stage_in) (void)hipHostFree(ws->stage_in);
-  if (ws->stage_out) (void)hipHostFree(ws->stage_out);
-  if (ws->stage_guess) (void)hipHostFree(ws->stage_guess);
+  ws->serve_box.release();
+  ws->stage_in.release();
+  ws->stage_out.release();
+  ws->stage_guess.release();
   if (ws->stage_stream) (void)hipStreamDestroy(ws->stage_stream);
   delete ws;
 }
@@ -409,6 +387,7 @@ int mpcqp_solve(mpcqp_ws* ws, int B, double* u0, double* X, double* U, int32_t* 
     return fail(MPCQP_E_STATE, "mpcqp_solve B differs from the last mpcqp_build");
   if (B == 0) return MPCQP_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
+  const mpcqp::HorizonKernels* k = mpcqp::one_wave(ws->p, true);  // nullptr: a workgroup-per-QP family
   Launch L{&ws->p, B, ws->model, ws->state, u0, X, U, status, iters, active, nullptr};
   L.x0 = built.x0;
   L.ref = built.ref;
@@ -418,10 +397,10 @@ int mpcqp_solve(mpcqp_ws* ws, int B, double* u0, double* X, double* U, int32_t* 
     L.cls = built.cls;
     L.K = ws->n_classes;
     // the workgroup-per-QP launchers read L.cls themselves; the one-wave kernel has an entry of its own
-    (mpcqp::wide_solve(ws->p) ? mpcqp::launcher(ws->p) : g_kernels[ws->p.horizon].mixed)(s, L);
+    (k ? k->mixed : mpcqp::launcher(ws->p))(s, L);
     return mpcqp::launched("k_solve_mixed");
   }
-  (L.ref && mpcqp::use_pairs(ws, B) ? g_kernels[ws->p.horizon].pair : mpcqp::launcher(ws->p))(s, L);
+  (L.ref && mpcqp::use_pairs(ws, B) ? k->pair : mpcqp::launcher(ws->p))(s, L);  // use_pairs: one wave, k->pair set
   return mpcqp::launched("k_solve");
 }
 
@@ -429,7 +408,7 @@ int mpcqp_solve_warm(mpcqp_ws* ws, int B, const double* U_guess, int guess_passe
                      int32_t* status, int32_t* iters, uint8_t* active, void* stream) {
   if (!ws || !status || !U_guess) return fail(MPCQP_E_ARG, "null argument");
   // the fused one-wave kernel only; refused before anything is enqueued
-  const mpcqp::HorizonKernels* k = mpcqp::one_wave(ws->p, false);
+  const mpcqp::HorizonKernels* k = mpcqp::one_wave(ws->p);
   if (!k || !k->warm)
     return fail(MPCQP_E_HORIZON, "mpcqp_solve_warm runs the fused one-wave kernel only (N <= 32, fast mode, no "
                                  "debug_state)");
@@ -465,19 +444,14 @@ int mpcqp_stage(mpcqp_ws* ws, double** in, void** out, int32_t offsets[6]) {
   const int N = ws->p.horizon;
   int32_t off[7];
   stage_offsets(N, off);
-  if (!ws->stage_in) {
+  if (!ws->stage_in.host) {  // both blocks and the stream, or none
     const mpcqp::DeviceGuard dev(ws->device);
     hipError_t e = dev.err;
-    const unsigned fl = hipHostMallocMapped | hipHostMallocCoherent;
-    double* hin = nullptr;
-    uint8_t* hout = nullptr;
-    void* din = nullptr;
-    void* dout = nullptr;
+    mpcqp::Mapped<double> hin;
+    mpcqp::Mapped<uint8_t> hout;
     hipStream_t st = nullptr;
-    if (e == hipSuccess) e = hipHostMalloc((void**)&hin, sizeof(double) * (size_t)(4 * (N + 1) + 6), fl);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&hout, (size_t)off[6], fl);
-    if (e == hipSuccess) e = hipHostGetDevicePointer(&din, hin, 0);
-    if (e == hipSuccess) e = hipHostGetDevicePointer(&dout, hout, 0);
+    if (e == hipSuccess) e = hin.alloc((size_t)(4 * (N + 1) + 6));
+    if (e == hipSuccess) e = hout.alloc((size_t)off[6]);
     // the highest stream priority: the runtime gives each priority its own hardware queues, so the
     // resident server wave of mpcqp_solve_served never sits in a queue that torch's (default-priority)
     // streams share -- a queued packet behind a resident kernel waits until it leaves
@@ -488,101 +462,82 @@ int mpcqp_stage(mpcqp_ws* ws, double** in, void** out, int32_t offsets[6]) {
     const bool dflt = pr && std::strcmp(pr, "default") == 0;
     if (e == hipSuccess) e = hipStreamCreateWithPriority(&st, hipStreamNonBlocking, dflt ? least : greatest);
     if (e != hipSuccess) {
-      if (hin) (void)hipHostFree(hin);
-      if (hout) (void)hipHostFree(hout);
+      hin.release();
+      hout.release();
       return fail(MPCQP_E_HIP, std::string("B=1 staging blocks: ") + hipGetErrorString(e));
     }
-    std::memset(hin, 0, sizeof(double) * (size_t)(4 * (N + 1) + 6));
-    std::memset(hout, 0, (size_t)off[6]);
     ws->stage_in = hin;
-    ws->stage_in_d = static_cast<double*>(din);
     ws->stage_out = hout;
-    ws->stage_out_d = static_cast<uint8_t*>(dout);
     ws->stage_stream = st;
   }
-  if (in) *in = ws->stage_in;
-  if (out) *out = ws->stage_out;
+  if (in) *in = ws->stage_in.host;
+  if (out) *out = ws->stage_out.host;
   if (offsets)
     for (int i = 0; i < 6; ++i) offsets[i] = off[i];
   return MPCQP_OK;
 }
 
-int mpcqp_solve_staged(mpcqp_ws* ws) {
-  if (!ws) return fail(MPCQP_E_ARG, "null ws");
-  if (!ws->stage_in) return fail(MPCQP_E_STATE, "mpcqp_solve_staged before mpcqp_stage");
+// The staged solve of mpcqp_solve_staged (guess == nullptr) and mpcqp_solve_staged_warm, after their
+// checks: build, solve and synchronise on the workspace's stream, in and out of its staging blocks.
+static int solve_staged(mpcqp_ws* ws, const double* guess, int guess_passes) {
   const int N = ws->p.horizon;
   int32_t off[7];
   stage_offsets(N, off);
-  const double* d = ws->stage_in_d;
-  uint8_t* o = ws->stage_out_d;
+  const double* d = ws->stage_in.dev;
+  uint8_t* o = ws->stage_out.dev;
+  double *u0 = reinterpret_cast<double*>(o + off[0]), *X = reinterpret_cast<double*>(o + off[1]),
+         *U = reinterpret_cast<double*>(o + off[2]);
+  int32_t *status = reinterpret_cast<int32_t*>(o + off[3]), *iters = reinterpret_cast<int32_t*>(o + off[4]);
   hipStream_t s = ws->stage_stream;
   int rc = mpcqp_build(ws, 1, d, d + 4, d + 4 + 4 * (N + 1), s);
   if (rc) return rc;
-  rc = mpcqp_solve(ws, 1, reinterpret_cast<double*>(o + off[0]), reinterpret_cast<double*>(o + off[1]),
-                   reinterpret_cast<double*>(o + off[2]), reinterpret_cast<int32_t*>(o + off[3]),
-                   reinterpret_cast<int32_t*>(o + off[4]), o + off[5], s);
+  rc = guess ? mpcqp_solve_warm(ws, 1, guess, guess_passes, u0, X, U, status, iters, o + off[5], s)
+             : mpcqp_solve(ws, 1, u0, X, U, status, iters, o + off[5], s);
   if (rc) return rc;
   const hipError_t e = hipStreamSynchronize(s);
   if (e != hipSuccess) return fail(MPCQP_E_DEVICE, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
   return MPCQP_OK;
+}
+
+int mpcqp_solve_staged(mpcqp_ws* ws) {
+  if (!ws) return fail(MPCQP_E_ARG, "null ws");
+  if (!ws->stage_in.host) return fail(MPCQP_E_STATE, "mpcqp_solve_staged before mpcqp_stage");
+  return solve_staged(ws, nullptr, 0);
 }
 
 // The guess block of the warm B = 1 calls: 2 x N doubles in the layout of U, then guess_passes (written by
 // mpcqp_solve_served_warm for the resident wave).  NaN until the caller writes it: an unusable guess.
 int mpcqp_stage_guess(mpcqp_ws* ws, double** guess) {
   if (!ws || !guess) return fail(MPCQP_E_ARG, "null argument");
-  if (!ws->stage_in) return fail(MPCQP_E_STATE, "mpcqp_stage_guess before mpcqp_stage");
-  if (!ws->stage_guess) {
+  if (!ws->stage_in.host) return fail(MPCQP_E_STATE, "mpcqp_stage_guess before mpcqp_stage");
+  if (!ws->stage_guess.host) {
     const int N = ws->p.horizon;
     const mpcqp::DeviceGuard dev(ws->device);
     hipError_t e = dev.err;
-    double* hg = nullptr;
-    void* dg = nullptr;
-    if (e == hipSuccess)
-      e = hipHostMalloc((void**)&hg, sizeof(double) * (size_t)(2 * N + 1), hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess) e = hipHostGetDevicePointer(&dg, hg, 0);
-    if (e != hipSuccess) {
-      if (hg) (void)hipHostFree(hg);
-      return fail(MPCQP_E_HIP, std::string("B=1 guess block: ") + hipGetErrorString(e));
-    }
-    for (int i = 0; i < 2 * N; ++i) hg[i] = std::numeric_limits<double>::quiet_NaN();
-    std::memset(hg + 2 * N, 0, sizeof(double));
-    ws->stage_guess = hg;
-    ws->stage_guess_d = static_cast<double*>(dg);
+    if (e == hipSuccess) e = ws->stage_guess.alloc((size_t)(2 * N + 1));
+    if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("B=1 guess block: ") + hipGetErrorString(e));
+    for (int i = 0; i < 2 * N; ++i) ws->stage_guess.host[i] = std::numeric_limits<double>::quiet_NaN();
   }
-  *guess = ws->stage_guess;
+  *guess = ws->stage_guess.host;
   return MPCQP_OK;
 }
 
 // the checks the two warm B = 1 calls share, in mpcqp_solve_warm's order: the kernel family, then the state
 static int staged_warm_check(mpcqp_ws* ws, const char* who) {
   if (!ws) return fail(MPCQP_E_ARG, "null ws");
-  const mpcqp::HorizonKernels* k = mpcqp::one_wave(ws->p, false);
+  const mpcqp::HorizonKernels* k = mpcqp::one_wave(ws->p);
   if (!k || !k->warm || !k->serve_warm)
     return fail(MPCQP_E_HORIZON, std::string(who) + " runs the fused one-wave kernel only (N <= 32, fast mode, no "
                                                     "debug_state)");
-  if (!ws->stage_in || !ws->stage_guess) return fail(MPCQP_E_STATE, std::string(who) + " before mpcqp_stage_guess");
+  if (!ws->stage_in.host || !ws->stage_guess.host)
+    return fail(MPCQP_E_STATE, std::string(who) + " before mpcqp_stage_guess");
   return MPCQP_OK;
 }
 
 int mpcqp_solve_staged_warm(mpcqp_ws* ws, int guess_passes) {
-  int rc = staged_warm_check(ws, "mpcqp_solve_staged_warm");
+  const int rc = staged_warm_check(ws, "mpcqp_solve_staged_warm");
   if (rc) return rc;
-  const int N = ws->p.horizon;
-  int32_t off[7];
-  stage_offsets(N, off);
-  const double* d = ws->stage_in_d;
-  uint8_t* o = ws->stage_out_d;
-  hipStream_t s = ws->stage_stream;
-  rc = mpcqp_build(ws, 1, d, d + 4, d + 4 + 4 * (N + 1), s);
-  if (rc) return rc;
-  rc = mpcqp_solve_warm(ws, 1, ws->stage_guess_d, guess_passes, reinterpret_cast<double*>(o + off[0]),
-                        reinterpret_cast<double*>(o + off[1]), reinterpret_cast<double*>(o + off[2]),
-                        reinterpret_cast<int32_t*>(o + off[3]), reinterpret_cast<int32_t*>(o + off[4]), o + off[5], s);
-  if (rc) return rc;
-  const hipError_t e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return fail(MPCQP_E_DEVICE, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
-  return MPCQP_OK;
+  return solve_staged(ws, ws->stage_guess.dev, guess_passes);
 }
 
 // One resident server wave per device: a workspace that raises a request first stops another
@@ -596,19 +551,21 @@ static mpcqp_ws* g_server[64] = {};
 // the number of the last completed request, after which the next one continues the sequence.  The
 // host's view (serve_seq, serve_live) is the caller's to update.
 static uint32_t serve_dismiss(mpcqp_ws* ws) {
-  auto* box = static_cast<mpcqp::ServeBox*>(ws->serve_box);
+  mpcqp::ServeBox* box = ws->serve_box.host;
   __atomic_store_n(&box->req, mpcqp::kServeStop, __ATOMIC_RELEASE);
   (void)hipStreamSynchronize(ws->stage_stream);
   const uint32_t done = __atomic_load_n(&box->done, __ATOMIC_ACQUIRE);
   __atomic_store_n(&box->req, done, __ATOMIC_RELEASE);
   return done;
 }
+// no other workspace's request stops (or counts on) this workspace's wave any more
+static void serve_forget(mpcqp_ws* ws) {
+  std::lock_guard<std::mutex> lk(g_serve_mu);
+  if (g_server[ws->device & 63] == ws) g_server[ws->device & 63] = nullptr;
+}
 // Ends a live server wave.  The caller holds ws->serve_mu.
 static void serve_stop_locked(mpcqp_ws* ws) {
-  {
-    std::lock_guard<std::mutex> lk(g_serve_mu);
-    if (g_server[ws->device & 63] == ws) g_server[ws->device & 63] = nullptr;
-  }
+  serve_forget(ws);
   if (!ws->serve_live) return;
   ws->serve_seq = serve_dismiss(ws);
   ws->serve_live = false;
@@ -625,8 +582,7 @@ static void serve_stop(mpcqp_ws* ws) {
 static int serve_request(mpcqp_ws* ws, bool warm, int guess_passes) {
   if (ws->serve_broken)
     return fail(MPCQP_E_DEVICE, "B=1 server: an earlier request went unanswered; this workspace is unusable");
-  const mpcqp::serve_t launch = mpcqp::server(ws->p);
-  const mpcqp::serve_warm_t launch_warm = mpcqp::server_warm(ws->p);
+  const mpcqp::HorizonKernels* k = mpcqp::one_wave(ws->p);  // the callers' checks: serve / serve_warm is there
   // this workspace's server state is ours for the whole call; another workspace's wave on this device
   // is stopped only when its own lock is free (try-lock, taken under g_serve_mu so that workspace cannot
   // be destroyed in between): a workspace busy in its own served call on another thread keeps its wave,
@@ -653,35 +609,26 @@ static int serve_request(mpcqp_ws* ws, bool warm, int guess_passes) {
     ws->serve_seq = serve_dismiss(ws);
     ws->serve_live = false;
   }
-  if (!ws->serve_box) {
+  if (!ws->serve_box.host) {
     const mpcqp::DeviceGuard dev(ws->device);
     hipError_t e = dev.err;
-    void* box = nullptr;
-    void* dbox = nullptr;
-    if (e == hipSuccess) e = hipHostMalloc(&box, sizeof(mpcqp::ServeBox), hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess) e = hipHostGetDevicePointer(&dbox, box, 0);
-    if (e != hipSuccess) {
-      if (box) (void)hipHostFree(box);
-      return fail(MPCQP_E_HIP, std::string("B=1 server mailbox: ") + hipGetErrorString(e));
-    }
-    std::memset(box, 0, sizeof(mpcqp::ServeBox));
-    ws->serve_box = box;
-    ws->serve_box_d = dbox;
+    if (e == hipSuccess) e = ws->serve_box.alloc(1);
+    if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("B=1 server mailbox: ") + hipGetErrorString(e));
     ws->serve_seq = 0;
   }
-  auto* box = static_cast<mpcqp::ServeBox*>(ws->serve_box);
+  mpcqp::ServeBox* box = ws->serve_box.host;
   uint32_t seq = ws->serve_seq + 1;
   if (seq == mpcqp::kServeStop) seq = 1;
   ws->serve_seq = seq;
-  if (warm) *reinterpret_cast<int32_t*>(ws->stage_guess + 2 * ws->p.horizon) = guess_passes;
+  if (warm) *reinterpret_cast<int32_t*>(ws->stage_guess.host + 2 * ws->p.horizon) = guess_passes;
   __atomic_store_n(&box->req, seq, __ATOMIC_RELEASE);  // after the caller's input (and guess) writes (x86: ordered)
   auto relaunch = [&]() -> int {
     int32_t off[7];
     stage_offsets(ws->p.horizon, off);
     mpcqp::ServeLaunch L{};
-    L.box = static_cast<mpcqp::ServeBox*>(ws->serve_box_d);
-    L.in = ws->stage_in_d;
-    L.out = ws->stage_out_d;
+    L.box = ws->serve_box.dev;
+    L.in = ws->stage_in.dev;
+    L.out = ws->stage_out.dev;
     for (int i = 0; i < 6; ++i) L.off[i] = off[i];
     L.idle_ticks = 200000;  // 2 ms at 100 MHz
     if (ws->serve_fault == 1) {  // mpcqp_debug_serve_fault: this launch is refused
@@ -689,10 +636,10 @@ static int serve_request(mpcqp_ws* ws, bool warm, int guess_passes) {
       return fail(MPCQP_E_HIP, "k_serve launch: refused (mpcqp_debug_serve_fault)");
     }
     if (warm) {
-      const int32_t* passes = reinterpret_cast<const int32_t*>(ws->stage_guess_d + 2 * ws->p.horizon);
-      launch_warm(ws->stage_stream, ws->p, mpcqp::ServeWarmLaunch{L, ws->stage_guess_d, passes});
+      const int32_t* passes = reinterpret_cast<const int32_t*>(ws->stage_guess.dev + 2 * ws->p.horizon);
+      k->serve_warm(ws->stage_stream, ws->p, mpcqp::ServeWarmLaunch{L, ws->stage_guess.dev, passes});
     } else {
-      launch(ws->stage_stream, ws->p, L);
+      k->serve(ws->stage_stream, ws->p, L);
     }
     if (const int rc = mpcqp::launched(warm ? "k_serve_warm" : "k_serve")) return rc;
     ws->serve_live = true;
@@ -731,10 +678,7 @@ static int serve_request(mpcqp_ws* ws, bool warm, int guess_passes) {
         __atomic_store_n(&box->req, mpcqp::kServeStop, __ATOMIC_RELEASE);
         ws->serve_live = false;
         ws->serve_broken = true;
-        {  // no other workspace's request stops (or counts on) this wave any more
-          std::lock_guard<std::mutex> lk(g_serve_mu);
-          if (g_server[ws->device & 63] == ws) g_server[ws->device & 63] = nullptr;
-        }
+        serve_forget(ws);
         return fail(MPCQP_E_DEVICE, "B=1 server: no answer within 30 s");
       }
     }
@@ -745,8 +689,9 @@ static int serve_request(mpcqp_ws* ws, bool warm, int guess_passes) {
 
 int mpcqp_solve_served(mpcqp_ws* ws) {
   if (!ws) return fail(MPCQP_E_ARG, "null ws");
-  if (!ws->stage_in) return fail(MPCQP_E_STATE, "mpcqp_solve_served before mpcqp_stage");
-  if (!mpcqp::server(ws->p)) return mpcqp_solve_staged(ws);  // long horizons, reproducible or debug builds
+  if (!ws->stage_in.host) return fail(MPCQP_E_STATE, "mpcqp_solve_served before mpcqp_stage");
+  const mpcqp::HorizonKernels* k = mpcqp::one_wave(ws->p);
+  if (!k || !k->serve) return mpcqp_solve_staged(ws);  // long horizons, reproducible or debug builds
   return serve_request(ws, false, 0);
 }
 

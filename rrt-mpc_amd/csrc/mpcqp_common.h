@@ -565,8 +565,6 @@ struct ServeLaunch {
   uint64_t idle_ticks;  // s_memrealtime ticks (100 MHz) without a request after which the wave exits
 };
 typedef void (*serve_t)(hipStream_t, const mpcqp_params&, const ServeLaunch&);
-// nullptr when the parameter block does not run the one-wave kernel; defined in mpcqp.hip
-serve_t server(const mpcqp_params& p);
 // The server from a caller's guess (mpcqp_solve_served_warm, k_serve_warm): k_serve's launch plus the
 // workspace's guess block (mpcqp_stage_guess): 2 x N doubles in the layout of U, and behind them the
 // request's guess_passes.  The host writes both before it raises box->req.
@@ -576,38 +574,42 @@ struct ServeWarmLaunch {
   const int32_t* passes;  // device address of guess_passes (the block's last 8 bytes)
 };
 typedef void (*serve_warm_t)(hipStream_t, const mpcqp_params&, const ServeWarmLaunch&);
-serve_warm_t server_warm(const mpcqp_params& p);  // nullptr as server()
-typedef void (*fleet_loop_t)(hipStream_t, const mpcqp_params*, const mpcqp_fleet&, int, const LoopTrigger&);
-// the fused loop with a class per vehicle: the table of 2K interleaved blocks, cls (V indices), K, the
-// fleet, steps, the dispatch order (or nullptr)
-typedef void (*fleet_loop_mixed_t)(hipStream_t, const mpcqp_params*, const int32_t*, int, const mpcqp_fleet&, int,
-                                   const int32_t*);
-// the warm-started fused loop: the two blocks, the fleet, steps, guess_passes, the dispatch order (or nullptr)
-typedef void (*fleet_loop_warm_t)(hipStream_t, const mpcqp_params*, const mpcqp_fleet&, int, int, const int32_t*);
+// One fused-loop launch (device pointers), the loops' counterpart of Launch: k_fleet_loop (tr.pair: two
+// vehicles per wave), k_fleet_loop_mixed (cls != nullptr) and k_fleet_loop_warm read what they need of it.
+struct LoopLaunch {
+  const mpcqp_params* P;  // {nominal, relaxed}; with cls the 2 K interleaved blocks {nominal[c], relaxed[c]}
+  const mpcqp_fleet* f;
+  int steps;
+  LoopTrigger tr;  // the mixed and warm loops read only its dispatch order
+  const int32_t* cls = nullptr;  // a class per vehicle (V indices) into the K classes
+  int K = 0;
+  int guess_passes = 0;  // the warm loop's pass limit per attempt
+};
+typedef void (*fleet_loop_t)(hipStream_t, const LoopLaunch&);
 // The kernels of one horizon of the one-wave family (N < MPCQP_WIDE_MIN_HORIZON; the launch_*<N>
 // templates of mpcqp_solve.h): k_solve, k_solve_mixed (a parameter block per QP), k_solve_pair (two
 // QPs per wave, fused K1; nullptr above kPairMaxHorizon), k_serve (the B = 1 server), k_fleet_loop
 // (the fused closed loop), k_fleet_loop_mixed (the same with a class per vehicle), k_solve_warm (from a
 // caller's guess), k_fleet_loop_warm (the fused loop, each step from the one before) and k_serve_warm
-// (the B = 1 server from a caller's guess).  The object that
-// instantiates a horizon registers it from a namespace-scope
-// initialiser (register_horizons, mpcqp_solve.h); an all-null entry is a horizon not compiled in.
+// (the B = 1 server from a caller's guess).  The object that instantiates a horizon registers it from
+// a namespace-scope initialiser (register_horizons, mpcqp_solve.h); an all-null entry is a horizon not
+// compiled in.
 struct HorizonKernels {
   launcher_t solve, mixed, pair;
   serve_t serve;
-  fleet_loop_t loop;
-  fleet_loop_mixed_t loop_mixed;
+  fleet_loop_t loop, loop_mixed;
   launcher_t warm;
-  fleet_loop_warm_t loop_warm;
+  fleet_loop_t loop_warm;
   serve_warm_t serve_warm;
 };
 // fills entry N of the table in mpcqp.hip (constant-initialised, so the order of the objects'
 // initialisers does not matter)
 void register_horizon(int N, const HorizonKernels& k);
-// nullptr when the parameter block does not run the one-wave kernel; defined in mpcqp.hip
-fleet_loop_t fleet_looper(const mpcqp_params& p);
-fleet_loop_mixed_t fleet_looper_mixed(const mpcqp_params& p);
-fleet_loop_warm_t fleet_looper_warm(const mpcqp_params& p);
+// The one read of that table: the one-wave kernels of the parameter block's horizon; nullptr when it
+// runs another kernel family (long horizons, reproducible mode) or, for the entry points that keep no
+// debug state, with debug_state.  A caller takes the member it needs and tests it for null (a horizon
+// not compiled in).  Defined in mpcqp.hip.
+const HorizonKernels* one_wave(const mpcqp_params& p, bool debug_ok = false);
 // k_solve_pair / k_fleet_loop<N, true> for `count` QPs or vehicles of this workspace's launch?
 bool use_pairs(const mpcqp_ws* ws, int count);
 // the long-horizon solve (N >= MPCQP_WIDE_MIN_HORIZON; mpcqp_wide.hip): one 256-thread workgroup
@@ -653,6 +655,31 @@ struct DeviceGuard {
   DeviceGuard(const DeviceGuard&) = delete;
   DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
+// `count` T of pinned host memory that the device reads and writes in place (mapped, coherent): the
+// blocks of the B = 1 path.  alloc() runs on the current device and zeroes the block; on failure
+// nothing is held.
+template <class T>
+struct Mapped {
+  T* host = nullptr;
+  T* dev = nullptr;  // the same block's device address
+  hipError_t alloc(size_t count) {
+    void *h = nullptr, *d = nullptr;
+    hipError_t e = hipHostMalloc(&h, sizeof(T) * count, hipHostMallocMapped | hipHostMallocCoherent);
+    if (e == hipSuccess) e = hipHostGetDevicePointer(&d, h, 0);
+    if (e != hipSuccess) {
+      if (h) (void)hipHostFree(h);
+      return e;
+    }
+    std::memset(h, 0, sizeof(T) * count);
+    host = static_cast<T*>(h);
+    dev = static_cast<T*>(d);
+    return hipSuccess;
+  }
+  void release() {
+    if (host) (void)hipHostFree(host);
+    host = dev = nullptr;
+  }
+};
 }  // namespace mpcqp
 
 // Workspace of one device: parameter block + per-QP model (K1 output) and solver state.
@@ -688,18 +715,14 @@ struct mpcqp_ws {
   // the fused loop's dispatch order (max_batch vehicles), written by k_fleet_order on the stream
   int32_t* dorder = nullptr;
   // the B = 1 path (mpcqp_stage / mpcqp_solve_staged): mapped host blocks and a private stream
-  double* stage_in = nullptr;      // host address (x0 | ref | u_prev)
-  double* stage_in_d = nullptr;    // its device address
-  uint8_t* stage_out = nullptr;    // host address (u0 | X | U | status | iters | active)
-  uint8_t* stage_out_d = nullptr;  // its device address
+  mpcqp::Mapped<double> stage_in;    // x0 | ref | u_prev
+  mpcqp::Mapped<uint8_t> stage_out;  // u0 | X | U | status | iters | active
   hipStream_t stage_stream = nullptr;
   // the guess block of the warm B = 1 calls (mpcqp_stage_guess): 2 x N doubles, then guess_passes (i32)
-  double* stage_guess = nullptr;    // host address
-  double* stage_guess_d = nullptr;  // its device address
-  bool serve_warm = false;          // the kind of the live server wave: k_serve_warm (else k_serve)
-  // the B = 1 server: mailbox (host / device address), sequence number, a server kernel enqueued
-  void* serve_box = nullptr;
-  void* serve_box_d = nullptr;
+  mpcqp::Mapped<double> stage_guess;
+  bool serve_warm = false;  // the kind of the live server wave: k_serve_warm (else k_serve)
+  // the B = 1 server: mailbox, sequence number, a server kernel enqueued
+  mpcqp::Mapped<mpcqp::ServeBox> serve_box;
   uint32_t serve_seq = 0;
   bool serve_live = false;
   bool serve_broken = false;  // a request went unanswered (30 s): the workspace refuses B = 1 requests
@@ -722,10 +745,16 @@ struct mpcqp_ws {
 };
 
 namespace mpcqp {
-// the fused fleet loop (mpcqp_fleet.hip), with the swarm's trigger when tr.max_replans > 0; *fused =
-// false (nothing enqueued) when the parameter blocks do not run the one-wave kernel
-int enqueue_fleet_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, int steps, const LoopTrigger& tr,
-                       hipStream_t s, bool* fused);
+// The fused loops (mpcqp_fleet.hip).  fused_loop: the member `which` (loop, loop_mixed, loop_warm) of
+// the horizon that both workspaces' parameter blocks run, or nullptr (another kernel family, debug
+// mode, not compiled in, or the two differ).  enqueue_fused_loop: one launch of it after the caller's
+// checks -- both builds invalidated, the parameter blocks stored on the stream (L.cls: the two class
+// tables, else the workspaces' own blocks; L.P is set here), the longest-first dispatch order when the
+// vehicles outnumber the wave slots (L.tr.order is set here), pairing under use_pairs where may_pair
+// (the plain loop), the launch, and `name` in its launch error.
+fleet_loop_t fused_loop(const mpcqp_ws* nominal, const mpcqp_ws* relaxed, fleet_loop_t HorizonKernels::*which);
+int enqueue_fused_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, fleet_loop_t loop, const char* name, bool may_pair,
+                       LoopLaunch L, hipStream_t s);
 // allocate ws->model / ws->state (max_batch QPs) if requested and not yet there; refuses to allocate
 // on a capturing stream (the first use must run outside a capture); defined in mpcqp.hip
 int ensure_buffers(mpcqp_ws* ws, bool model, bool state, hipStream_t s);

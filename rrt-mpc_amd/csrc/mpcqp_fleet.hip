@@ -270,26 +270,32 @@ int replay_graph(const char* what, hipStream_t user, int steps, const std::funct
   return rc;
 }
 
-// the fused loop with the swarm's trigger (tr.max_replans > 0, mpcqp_swarm_loop) or without; nullptr
-// looper (mid / long horizons, reproducible or debug mode): *fused = false, nothing enqueued
-int enqueue_fleet_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, int steps, const LoopTrigger& tr,
-                       hipStream_t s, bool* fused) {
-  const mpcqp::fleet_loop_t loop = mpcqp::fleet_looper(nominal->p);
-  *fused = loop && mpcqp::fleet_looper(relaxed->p) == loop;
-  if (!*fused) return MPCQP_OK;
+fleet_loop_t fused_loop(const mpcqp_ws* nominal, const mpcqp_ws* relaxed, fleet_loop_t HorizonKernels::*which) {
+  const HorizonKernels *kn = one_wave(nominal->p), *kr = one_wave(relaxed->p);
+  return kn && kr && kn->*which == kr->*which ? kn->*which : nullptr;
+}
+
+int enqueue_fused_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, fleet_loop_t loop, const char* name, bool may_pair,
+                       LoopLaunch L, hipStream_t s) {
   nominal->invalidate();  // as mpcqp_fleet_step: a later mpcqp_solve needs its own build
   relaxed->invalidate();
-  hipLaunchKernelGGL(k_store_params, dim3(1), dim3(kWave), 0, s, nominal->p, relaxed->p, nominal->dparams);
-  LoopTrigger tro = tr;
+  if (L.cls) {
+    L.P = nominal->dloop_classes;
+    hipLaunchKernelGGL(k_store_classes, dim3(L.K), dim3(kWave), 0, s, nominal->dclasses, relaxed->dclasses, L.K,
+                       nominal->dloop_classes);
+  } else {
+    L.P = nominal->dparams;
+    hipLaunchKernelGGL(k_store_params, dim3(1), dim3(kWave), 0, s, nominal->p, relaxed->p, nominal->dparams);
+  }
   // longest first only when the vehicles outnumber the wave slots (2 per SIMD): with every vehicle
   // resident at once the order only changes which vehicles share a SIMD (measured: no gain)
-  if (nominal->cus > 0 && f->vehicles > 8 * nominal->cus) {
-    hipLaunchKernelGGL(k_fleet_order, dim3(1), dim3(kOrderBuckets), 0, s, *f, nominal->dorder);
-    tro.order = nominal->dorder;
+  if (nominal->cus > 0 && L.f->vehicles > 8 * nominal->cus) {
+    hipLaunchKernelGGL(k_fleet_order, dim3(1), dim3(kOrderBuckets), 0, s, *L.f, nominal->dorder);
+    L.tr.order = nominal->dorder;
   }
-  tro.pair = mpcqp::use_pairs(nominal, f->vehicles);
-  loop(s, nominal->dparams, *f, steps, tro);
-  return launched("k_fleet_loop");
+  L.tr.pair = may_pair && use_pairs(nominal, L.f->vehicles);
+  loop(s, L);
+  return launched(name);
 }
 }  // namespace mpcqp
 
@@ -301,10 +307,9 @@ int mpcqp_fleet_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f,
   if (steps < 0) return fail(MPCQP_E_ARG, "steps must be >= 0");
   if (f->vehicles == 0 || steps == 0) return MPCQP_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  bool fused = false;
-  rc = mpcqp::enqueue_fleet_loop(nominal, relaxed, f, steps, mpcqp::LoopTrigger{0.0, 0, nullptr, nullptr}, s, &fused);
-  if (rc || fused) return rc;
-  return run_graph(nominal, relaxed, f, steps, s);  // mid / long horizons, reproducible or debug mode
+  const mpcqp::fleet_loop_t loop = mpcqp::fused_loop(nominal, relaxed, &mpcqp::HorizonKernels::loop);
+  if (!loop) return run_graph(nominal, relaxed, f, steps, s);  // mid / long horizons, reproducible or debug mode
+  return mpcqp::enqueue_fused_loop(nominal, relaxed, loop, "k_fleet_loop", true, {nullptr, f, steps}, s);
 }
 
 int mpcqp_fleet_loop_mixed(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const int32_t* cls, int steps,
@@ -314,8 +319,8 @@ int mpcqp_fleet_loop_mixed(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fle
   if (rc) return rc;
   if (steps < 0) return fail(MPCQP_E_ARG, "steps must be >= 0");
   // the fused one-wave kernel only; refused before anything is enqueued or invalidated
-  const mpcqp::fleet_loop_mixed_t loop = mpcqp::fleet_looper_mixed(nominal->p);
-  if (!loop || mpcqp::fleet_looper_mixed(relaxed->p) != loop)
+  const mpcqp::fleet_loop_t loop = mpcqp::fused_loop(nominal, relaxed, &mpcqp::HorizonKernels::loop_mixed);
+  if (!loop)
     return fail(MPCQP_E_HORIZON, "mpcqp_fleet_loop_mixed runs the fused one-wave loop only (N <= 32, fast mode, no "
                                  "debug_state): the stepped fleet has no per-vehicle classes");
   const int K = nominal->n_classes;
@@ -342,17 +347,10 @@ int mpcqp_fleet_loop_mixed(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fle
     nominal->dloop_classes = table;
     nominal->dloop_cap = K;
   }
-  nominal->invalidate();  // as mpcqp_fleet_loop: a later mpcqp_solve needs its own build
-  relaxed->invalidate();
-  hipLaunchKernelGGL(k_store_classes, dim3(K), dim3(kWave), 0, s, nominal->dclasses, relaxed->dclasses, K,
-                     nominal->dloop_classes);
-  const int32_t* order = nullptr;
-  if (nominal->cus > 0 && f->vehicles > 8 * nominal->cus) {  // longest first, as mpcqp_fleet_loop
-    hipLaunchKernelGGL(k_fleet_order, dim3(1), dim3(kOrderBuckets), 0, s, *f, nominal->dorder);
-    order = nominal->dorder;
-  }
-  loop(s, nominal->dloop_classes, cls, K, *f, steps, order);
-  return mpcqp::launched("k_fleet_loop_mixed");
+  mpcqp::LoopLaunch L{nullptr, f, steps};
+  L.cls = cls;
+  L.K = K;
+  return mpcqp::enqueue_fused_loop(nominal, relaxed, loop, "k_fleet_loop_mixed", false, L, s);
 }
 
 int mpcqp_fleet_loop_warm(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, int steps, int guess_passes,
@@ -361,22 +359,14 @@ int mpcqp_fleet_loop_warm(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_flee
   if (rc) return rc;
   if (steps < 0) return fail(MPCQP_E_ARG, "steps must be >= 0");
   // the fused one-wave kernel only; refused before anything is enqueued or invalidated
-  const mpcqp::fleet_loop_warm_t loop = mpcqp::fleet_looper_warm(nominal->p);
-  if (!loop || mpcqp::fleet_looper_warm(relaxed->p) != loop)
+  const mpcqp::fleet_loop_t loop = mpcqp::fused_loop(nominal, relaxed, &mpcqp::HorizonKernels::loop_warm);
+  if (!loop)
     return fail(MPCQP_E_HORIZON, "mpcqp_fleet_loop_warm runs the fused one-wave loop only (N <= 32, fast mode, no "
                                  "debug_state): the stepped fleet takes no guess");
   if (f->vehicles == 0 || steps == 0) return MPCQP_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  nominal->invalidate();  // as mpcqp_fleet_loop: a later mpcqp_solve needs its own build
-  relaxed->invalidate();
-  hipLaunchKernelGGL(k_store_params, dim3(1), dim3(kWave), 0, s, nominal->p, relaxed->p, nominal->dparams);
-  const int32_t* order = nullptr;
-  if (nominal->cus > 0 && f->vehicles > 8 * nominal->cus) {  // longest first, as mpcqp_fleet_loop
-    hipLaunchKernelGGL(k_fleet_order, dim3(1), dim3(kOrderBuckets), 0, s, *f, nominal->dorder);
-    order = nominal->dorder;
-  }
-  loop(s, nominal->dparams, *f, steps, guess_passes, order);
-  return mpcqp::launched("k_fleet_loop_warm");
+  mpcqp::LoopLaunch L{nullptr, f, steps};
+  L.guess_passes = guess_passes;
+  return mpcqp::enqueue_fused_loop(nominal, relaxed, loop, "k_fleet_loop_warm", false, L, static_cast<hipStream_t>(stream));
 }
 
 int mpcqp_fleet_run(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, int steps, int use_graph,

@@ -2438,19 +2438,20 @@ void launch_solve_mixed(hipStream_t s, const Launch& L) {
                      L.u0, L.X, L.U, L.st, L.it, L.ac);
 }
 template <int N>
-void launch_fleet_loop(hipStream_t s, const mpcqp_params* P, const mpcqp_fleet& f, int steps, const LoopTrigger& tr) {
+void launch_fleet_loop(hipStream_t s, const LoopLaunch& L) {
+  const mpcqp_fleet& f = *L.f;
   if constexpr (2 * N <= 30) {
-    if (tr.pair) {
-      hipLaunchKernelGGL((k_fleet_loop<N, true>), dim3((f.vehicles + 1) / 2), dim3(kWave), 0, s, P, f, steps, tr);
+    if (L.tr.pair) {
+      hipLaunchKernelGGL((k_fleet_loop<N, true>), dim3((f.vehicles + 1) / 2), dim3(kWave), 0, s, L.P, f, L.steps, L.tr);
       return;
     }
   }
-  hipLaunchKernelGGL(k_fleet_loop<N>, dim3(f.vehicles), dim3(kWave), 0, s, P, f, steps, tr);
+  hipLaunchKernelGGL(k_fleet_loop<N>, dim3(f.vehicles), dim3(kWave), 0, s, L.P, f, L.steps, L.tr);
 }
 template <int N>
-void launch_fleet_loop_mixed(hipStream_t s, const mpcqp_params* P, const int32_t* cls, int K, const mpcqp_fleet& f,
-                             int steps, const int32_t* order) {
-  hipLaunchKernelGGL(k_fleet_loop_mixed<N>, dim3(f.vehicles), dim3(kWave), 0, s, P, cls, K, f, steps, order);
+void launch_fleet_loop_mixed(hipStream_t s, const LoopLaunch& L) {
+  hipLaunchKernelGGL(k_fleet_loop_mixed<N>, dim3(L.f->vehicles), dim3(kWave), 0, s, L.P, L.cls, L.K, *L.f, L.steps,
+                     L.tr.order);
 }
 // from a caller's guess (L.guess, L.guess_passes; fused K1, no debug state)
 template <int N>
@@ -2459,9 +2460,9 @@ void launch_solve_warm(hipStream_t s, const Launch& L) {
                      L.guess_passes, L.u0, L.X, L.U, L.st, L.it, L.ac);
 }
 template <int N>
-void launch_fleet_loop_warm(hipStream_t s, const mpcqp_params* P, const mpcqp_fleet& f, int steps, int guess_passes,
-                            const int32_t* order) {
-  hipLaunchKernelGGL(k_fleet_loop_warm<N>, dim3(f.vehicles), dim3(kWave), 0, s, P, f, steps, guess_passes, order);
+void launch_fleet_loop_warm(hipStream_t s, const LoopLaunch& L) {
+  hipLaunchKernelGGL(k_fleet_loop_warm<N>, dim3(L.f->vehicles), dim3(kWave), 0, s, L.P, *L.f, L.steps, L.guess_passes,
+                     L.tr.order);
 }
 // two QPs per wave (N <= kPairMaxHorizon, fused K1, no debug state)
 template <int N>

@@ -274,13 +274,13 @@ int mpcqp_swarm_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f,
   if (s->max_replans > 0 && (rc = set_replan_attrs(s)) != MPCQP_OK) return rc;
   // max_replans + 1 rounds: every vehicle runs until it triggers or ends, the flagged ones are
   // replanned; a vehicle's r-th trigger comes in round r - 1, so the last round triggers none
+  const mpcqp::fleet_loop_t loop = mpcqp::fused_loop(nominal, relaxed, &mpcqp::HorizonKernels::loop);
+  if (!loop)  // mid / long horizons, reproducible or debug mode: the stepped swarm to the end
+    return mpcqp_swarm_run(nominal, relaxed, f, s, f->max_steps, 1, stream);
   const mpcqp::LoopTrigger tr{s->replan_distance, s->max_replans, s->replans, s->start_goal};
   for (int r = 0; r <= s->max_replans; ++r) {
-    bool fused = false;
-    rc = mpcqp::enqueue_fleet_loop(nominal, relaxed, f, f->max_steps, tr, st, &fused);
+    rc = mpcqp::enqueue_fused_loop(nominal, relaxed, loop, "k_fleet_loop", true, {nullptr, f, f->max_steps, tr}, st);
     if (rc) return rc;
-    if (!fused)  // mid / long horizons, reproducible or debug mode: the stepped swarm to the end
-      return mpcqp_swarm_run(nominal, relaxed, f, s, f->max_steps, 1, stream);
     if (r < s->max_replans && (rc = enqueue_replan(f, s, st, false)) != MPCQP_OK) return rc;
   }
   return MPCQP_OK;

@@ -365,10 +365,19 @@ def lib() -> ctypes.CDLL:
     return handle
 
 
+def raise_failed(rc: int, what: str, exc=LibraryError, sync_fault: bool = False):
+    """Raises ``exc("<what> failed (<rc>): <mpcqp_last_error()>")`` for a call that returned ``rc`` != 0;
+    with ``sync_fault`` a fault that surfaced at the call's synchronisation (``E_DEVICE``) is a
+    ``DeviceError("<what>: <mpcqp_last_error()>")`` instead."""
+    msg = lib().mpcqp_last_error().decode(errors="replace")
+    if sync_fault and rc == E_DEVICE:
+        raise DeviceError(f"{what}: {msg}")
+    raise exc(f"{what} failed ({rc}): {msg}")
+
+
 def check(rc: int, what: str) -> None:
     if rc != 0:
-        msg = lib().mpcqp_last_error().decode(errors="replace")
-        raise LibraryError(f"{what} failed ({rc}): {msg}")
+        raise_failed(rc, what)
 
 
 __all__ = [
@@ -391,6 +400,7 @@ __all__ = [
     "FLEET_OUT_OF_STEPS",
     "lib",
     "check",
+    "raise_failed",
     "LibraryError",
     "DeviceError",
     "DEFAULT_SOLVER_SETTINGS",

@@ -329,10 +329,7 @@ class BatchedMPCController:
             io["up"][:] = u_prev
         rc = solve1(self._ws)
         if rc != 0:
-            msg = self._L.mpcqp_last_error().decode(errors="replace")
-            if rc == _lib.E_DEVICE:
-                raise _lib.DeviceError(f"B=1 solve: {msg}")
-            raise _lib.LibraryError(f"B=1 solve failed ({rc}): {msg}")
+            _lib.raise_failed(rc, "B=1 solve", sync_fault=True)
         return int(io["status"][0]), io["u0"].copy(), io["X"].copy(), io["U"].copy()
 
     _one = None
@@ -351,8 +348,7 @@ class BatchedMPCController:
         with self._torch.cuda.device(self.device):
             rc = self._L.mpcqp_stage_guess(self._ws, ctypes.byref(hg))
         if rc != 0:
-            raise _lib.DeviceError(f"mpcqp_stage_guess failed ({rc}): "
-                                   f"{self._L.mpcqp_last_error().decode(errors='replace')}")
+            _lib.raise_failed(rc, "mpcqp_stage_guess", _lib.DeviceError)
         N = self.horizon
         return np.frombuffer((ctypes.c_double * (2 * N)).from_address(hg.value), np.float64).reshape(2, N)
 
@@ -371,7 +367,7 @@ class BatchedMPCController:
         with self._torch.cuda.device(self.device):
             rc = self._L.mpcqp_stage(self._ws, ctypes.byref(hin), ctypes.byref(hout), offs)
         if rc != 0:
-            raise _lib.DeviceError(f"mpcqp_stage failed ({rc}): {self._L.mpcqp_last_error().decode(errors='replace')}")
+            _lib.raise_failed(rc, "mpcqp_stage", _lib.DeviceError)
         nin = 4 + 4 * (N + 1) + 2
         nout = offs[5] + 5 * N + 1
         fin = np.frombuffer((ctypes.c_double * nin).from_address(hin.value), np.float64)

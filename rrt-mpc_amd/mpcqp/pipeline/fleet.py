@@ -222,11 +222,7 @@ class FleetTracker:
         if V > self.max_vehicles:
             raise ValueError(f"{V} vehicles exceed max_vehicles {self.max_vehicles}")
         cls = self._class_indices(classes, V)
-        states0 = np.asarray(states0, dtype=float).reshape(V, 4)
-        goals = np.asarray(goals, dtype=float).reshape(V, 2)
-        max_steps = int(self.mpc.sim_steps if max_steps is None else max_steps)
-        if max_steps < 1:
-            raise ValueError("max_steps must be >= 1")
+        start = self._start_inputs(V, states0, goals, max_steps)
         lens = np.array([len(r) for r in ref_globals], dtype=np.int32)
         if V and (lens.min() < 1 or lens.max() > self.max_ref_len):
             raise ValueError(f"reference lengths must be in [1, {self.max_ref_len}]")
@@ -237,18 +233,24 @@ class FleetTracker:
             if r.ndim != 2 or r.shape[1] != 4:
                 raise ValueError("each reference must have shape (M, 4)")
             ref[v, : len(r)] = r
-        self._load(V, ref, lens, states0, goals, max_steps, cls)
+        self._load(V, ref, lens, *start, cls)
 
-    def _load(self, V: int, ref: Optional[np.ndarray], lens: np.ndarray, states0: np.ndarray, goals: np.ndarray,
-              max_steps: Optional[int], cls=None) -> None:
-        """The fleet's device buffers for V vehicles; ``ref`` None: the references are copied in on the
-        device afterwards (reset_device), so no host copy of them is built or uploaded."""
-        torch = self._torch
+    def _start_inputs(self, V: int, states0, goals, max_steps: Optional[int]):
+        """``(states0 (V, 4), goals (V, 2), max_steps)`` as ``_load`` takes them (``max_steps`` None: the
+        config's ``sim_steps``)."""
         states0 = np.asarray(states0, dtype=float).reshape(V, 4)
         goals = np.asarray(goals, dtype=float).reshape(V, 2)
         max_steps = int(self.mpc.sim_steps if max_steps is None else max_steps)
         if max_steps < 1:
             raise ValueError("max_steps must be >= 1")
+        return states0, goals, max_steps
+
+    def _load(self, V: int, ref: Optional[np.ndarray], lens: np.ndarray, states0: np.ndarray, goals: np.ndarray,
+              max_steps: int, cls=None) -> None:
+        """The fleet's device buffers for V vehicles (the inputs as ``_start_inputs`` returns them);
+        ``ref`` None: the references are copied in on the device afterwards (reset_device), so no host
+        copy of them is built or uploaded."""
+        torch = self._torch
         M = self.max_ref_len
         N = self.horizon
         dev = dict(device=self.device)
@@ -326,7 +328,7 @@ class FleetTracker:
         if V and (lens.min() < 1 or lens.max() > self.max_ref_len):
             raise ValueError(f"reference lengths must be in [1, {self.max_ref_len}] (build_reference_batch "
                              f"reports overflow as negative lengths)")
-        self._load(V, None, lens.astype(np.int32), states0, goals, max_steps, cls)
+        self._load(V, None, lens.astype(np.int32), *self._start_inputs(V, states0, goals, max_steps), cls)
         self._bufs["ref_global"][:V].copy_(ref)
         self._bufs["ref_len"][:V].copy_(ref_len.to(torch.int32))
 
@@ -339,21 +341,16 @@ class FleetTracker:
         if stream is None:
             stream = torch.cuda.current_stream(self.device)
         s = ctypes.c_void_p(stream.cuda_stream)
+        fleet = (self._nominal._ws, self._relaxed._ws, ctypes.byref(self._fleet))
         if self.num_classes:  # a class per vehicle (set_classes: fused only)
-            _lib.check(self._L.mpcqp_fleet_loop_mixed(self._nominal._ws, self._relaxed._ws, ctypes.byref(self._fleet),
-                                                      self._bufs["cls"].data_ptr(), int(steps), s),
-                       "mpcqp_fleet_loop_mixed")
-            return
-        if self.warm_start:  # fused, each step's solves started from the step before (cold at every launch)
-            _lib.check(self._L.mpcqp_fleet_loop_warm(self._nominal._ws, self._relaxed._ws, ctypes.byref(self._fleet),
-                                                     int(steps), self.guess_passes, s), "mpcqp_fleet_loop_warm")
-            return
-        if self.fused:
-            _lib.check(self._L.mpcqp_fleet_loop(self._nominal._ws, self._relaxed._ws, ctypes.byref(self._fleet),
-                                                int(steps), s), "mpcqp_fleet_loop")
-            return
-        _lib.check(self._L.mpcqp_fleet_run(self._nominal._ws, self._relaxed._ws, ctypes.byref(self._fleet),
-                                           int(steps), int(self.use_graph), s), "mpcqp_fleet_run")
+            call, args = "mpcqp_fleet_loop_mixed", (self._bufs["cls"].data_ptr(), int(steps))
+        elif self.warm_start:  # fused, each step's solves started from the step before (cold at every launch)
+            call, args = "mpcqp_fleet_loop_warm", (int(steps), self.guess_passes)
+        elif self.fused:
+            call, args = "mpcqp_fleet_loop", (int(steps),)
+        else:
+            call, args = "mpcqp_fleet_run", (int(steps), int(self.use_graph))
+        _lib.check(getattr(self._L, call)(*fleet, *args, s), call)
 
     def running(self) -> int:
         return int((self._bufs["phase"][: self.vehicles] == _lib.FLEET_RUNNING).sum().item())

@@ -10,21 +10,13 @@ from pathlib import Path
 
 import numpy as np
 import pytest
+from host_helpers import E_ARG
+from host_helpers import bare_controller as _bare_controller
+from host_helpers import binding as _binding
 from param_variants import VARIANTS, resolution, variant
 
 ROOT = Path(__file__).resolve().parents[1]
 HEADER = ROOT / "include" / "mpcqp.h"
-E_ARG, E_STATE = -1, -5
-
-
-def _binding():
-    import __graft_entry__ as g
-
-    if not g.LIB.exists():
-        g.build_library()
-    from mpcqp import _lib
-
-    return _lib
 
 
 def _variants(N):
@@ -115,19 +107,6 @@ def test_class_table_refuses_what_the_library_would():
         class_table(plist[:2], settings=[{}, dict(reproducible=1)])
     with pytest.raises(ValueError, match="at least one"):
         class_table([])
-
-
-def _bare_controller(N=10, max_batch=8, num_classes=0):
-    """A controller object without a workspace (no device here): what the argument checks read."""
-    import torch
-    from mpcqp.control.mpc_controller import BatchedMPCController
-
-    c = object.__new__(BatchedMPCController)
-    c._torch = torch
-    c.device = torch.device("cpu")
-    c.horizon, c.max_batch, c.num_classes = N, max_batch, num_classes
-    c._ws = ctypes.c_void_p()  # null: close() / __del__ have nothing to destroy
-    return c
 
 
 def test_solve_batch_classes_argument_checks():

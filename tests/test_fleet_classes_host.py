@@ -11,21 +11,12 @@ from pathlib import Path
 
 import numpy as np
 import pytest
+from host_helpers import E_ARG
+from host_helpers import binding as _binding
 
 ROOT = Path(__file__).resolve().parents[1]
 HEADER = ROOT / "include" / "mpcqp.h"
 RESOURCES = ROOT / "build" / "kernel_resources.json"
-E_ARG = -1
-
-
-def _binding():
-    import __graft_entry__ as g
-
-    if not g.LIB.exists():
-        g.build_library()
-    from mpcqp import _lib
-
-    return _lib
 
 
 def test_header_declares_and_library_exports_the_mixed_loop():

@@ -288,3 +288,68 @@ def test_fused_loop_dispatch_order_past_the_wave_slots(cuda, golden):
         ft.close()
     for k in _LOOP_BUFFERS:
         np.testing.assert_array_equal(bufs[0][k], bufs[1][k], err_msg=k)
+
+
+@pytest.mark.parametrize("entry", ["plain", "mixed", "warm"])
+def test_fused_loop_calls_that_enqueue_nothing_keep_the_build(cuda, golden, entry):
+    """A fused-loop entry point called raw: a call that enqueues nothing (steps = 0, or for the mixed and warm
+    entries a workspace in reproducible mode, refused with MPCQP_E_HORIZON) leaves both workspaces' builds
+    to a later mpcqp_solve, which answers as the first solve did bit for bit; a call that runs steps
+    invalidates them (MPCQP_E_STATE)."""
+    import ctypes
+
+    import torch
+
+    E_HORIZON, E_STATE = -2, -5
+    N = V = 3
+    _, paths, starts, goals = _varied_fleet(golden, V, seed=37)
+    x0 = np.tile([10.0, 10.0, 0.0, 5.0], (V, 1))
+    ref = np.tile(np.array([[10.0 + 1.5 * k, 10.0, 0.0, 15.0] for k in range(N + 1)]), (V, 1, 1))
+
+    def loop(ft, steps):
+        s = ctypes.c_void_p(torch.cuda.current_stream(ft.device).cuda_stream)
+        fleet = (ft._nominal._ws, ft._relaxed._ws, ctypes.byref(ft._fleet))
+        if entry == "mixed":
+            return ft._L.mpcqp_fleet_loop_mixed(*fleet, ft.buffers()["cls"].data_ptr(), steps, s)
+        if entry == "warm":
+            return ft._L.mpcqp_fleet_loop_warm(*fleet, steps, 2, s)
+        return ft._L.mpcqp_fleet_loop(*fleet, steps, s)
+
+    def outputs(ctrl):
+        return (ctrl._u0, ctrl._X, ctrl._U, ctrl._status, ctrl._iters, ctrl._active)
+
+    def solve_again(ctrl):  # a raw mpcqp_solve of the workspace's build into cleared outputs
+        for t in outputs(ctrl):
+            t.zero_()
+        s = ctypes.c_void_p(torch.cuda.current_stream(ctrl.device).cuda_stream)
+        rc = ctrl._L.mpcqp_solve(ctrl._ws, V, *(t.data_ptr() for t in outputs(ctrl)), s)
+        torch.cuda.synchronize()
+        return rc, [t.cpu().numpy().copy() for t in outputs(ctrl)]
+
+    modes = [({}, 0)] + ([(dict(reproducible=1), E_HORIZON)] if entry != "plain" else [])
+    for settings, refused in modes:
+        ft = _tracker(N, V, 128, 12, fused=True, **settings)
+        if entry == "mixed":
+            ft.set_classes([ft.params, ft.params])
+        ft.reset_from_plans(paths, starts, goals)
+        ctrls = (ft._nominal, ft._relaxed)
+        first = []
+        for ctrl in ctrls:
+            ctrl.solve_batch(x0, ref)
+            torch.cuda.synchronize()
+            first.append([t.cpu().numpy().copy() for t in outputs(ctrl)])
+            assert (first[-1][3] != 0).all(), first[-1][3]  # a status is never 0: a cleared buffer shows
+        for steps in ((0, 2) if refused else (0,)):
+            assert loop(ft, steps) == refused, (settings, steps, ft._L.mpcqp_last_error())
+            for ctrl, want in zip(ctrls, first):
+                rc, got = solve_again(ctrl)
+                assert rc == 0, (settings, steps, rc, ctrl._L.mpcqp_last_error())
+                for a, b in zip(got, want):
+                    np.testing.assert_array_equal(a, b)
+        if not refused:
+            assert loop(ft, 2) == 0, ft._L.mpcqp_last_error()
+            torch.cuda.synchronize()
+            assert (ft.buffers()["steps"].cpu().numpy()[:V] == 2).all()
+            for ctrl in ctrls:
+                assert solve_again(ctrl)[0] == E_STATE
+        ft.close()

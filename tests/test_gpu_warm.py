@@ -368,3 +368,34 @@ def test_warm_loop_relaxation_branches(cuda, golden):
     loop = golden("closed_loop.npz")
     for v in others:
         np.testing.assert_allclose(rw.states[v], loop["N10_states"][:steps], rtol=0, atol=ATOL)
+
+
+def test_warm_loop_longest_first_dispatch_order(cuda, golden):
+    """More vehicles than wave slots (8 per CU): the warm loop dispatches through the order table as the
+    plain loop does.  Without passes every step is cold (include/mpcqp.h): the plain fused loop's buffers bit
+    for bit; with the default passes the same phases, step counts and path indices."""
+    import torch
+    from mpcqp.control.ref_builder import build_reference
+    from mpcqp.pipeline.fleet import initial_states
+
+    N, steps = 3, 4
+    V = 8 * torch.cuda.get_device_properties(0).multi_processor_count + 5
+    paths, starts, goals = _varied_fleet(golden, V, seed=6)
+    s0 = initial_states(paths, starts)
+    out, refs = [], None
+    for kw in ({}, dict(warm_start=True, guess_passes=0), dict(warm_start=True)):
+        ft = _tracker(N, V, 128, steps, **kw)
+        if refs is None:  # _varied_fleet cycles through 13 plans: one reference per plan, built once
+            distinct = [build_reference(paths[i], ft.mpc.v_px_s, N, ft.mpc.dt) for i in range(13)]
+            assert all(paths[v] is paths[v - 13] for v in range(13, 26))
+            refs = [distinct[v % 13] for v in range(V)]
+        ft.reset(refs, s0, goals)
+        ft.run()
+        out.append({k: ft.buffers()[k].cpu().numpy().copy() for k in _LOOP_BUFFERS})
+        ft.close()
+    plain, cold, warm = out
+    assert (plain["steps"] == steps).any()
+    for k in _LOOP_BUFFERS:
+        np.testing.assert_array_equal(cold[k], plain[k], err_msg=k)
+    for k in ("phase", "steps", "path_idx"):
+        np.testing.assert_array_equal(warm[k], plain[k], err_msg=k)

@@ -10,19 +10,11 @@ from pathlib import Path
 
 import numpy as np
 import pytest
+from host_helpers import E_ARG, E_HIP, E_HORIZON, OK
+from host_helpers import binding as _binding
 
 ROOT = Path(__file__).resolve().parents[1]
 HEADER = ROOT / "include" / "mpcqp.h"
-
-
-def _binding():
-    import __graft_entry__ as g
-
-    if not g.LIB.exists():
-        g.build_library()
-    from mpcqp import _lib
-
-    return _lib
 
 
 def test_library_build_id_matches_the_sources():
@@ -412,7 +404,6 @@ def test_argument_checks_without_a_device():
 
     _lib_mod = _binding()
     L = _lib_mod.lib()
-    E_ARG = -1
     assert L.mpcqp_set_pairing(None, _lib_mod.PAIR_ON) == E_ARG
     assert b"null ws" in L.mpcqp_last_error()
     assert L.mpcqp_solve_served(None) == E_ARG
@@ -430,7 +421,6 @@ def test_every_horizon_is_compiled_in():
 
     _lib_mod = _binding()
     L = _lib_mod.lib()
-    OK, E_HORIZON, E_HIP = 0, -2, -4
     for N in range(1, 65):
         cp = _lib_mod.to_c_params(MPCConfig(horizon=N).to_parameters(0.8))
         ws = ctypes.c_void_p()

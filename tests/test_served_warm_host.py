@@ -14,22 +14,13 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 import warm_newton as wn
+from host_helpers import E_ARG
+from host_helpers import binding as _binding
 
 ROOT = Path(__file__).resolve().parents[1]
 HEADER = ROOT / "include" / "mpcqp.h"
 RESOURCES = ROOT / "build" / "kernel_resources.json"
-E_ARG = -1
 CALLS = ("mpcqp_stage_guess", "mpcqp_solve_staged_warm", "mpcqp_solve_served_warm")
-
-
-def _binding():
-    import __graft_entry__ as g
-
-    if not g.LIB.exists():
-        g.build_library()
-    from mpcqp import _lib
-
-    return _lib
 
 
 def test_header_declares_and_library_exports_the_b1_warm_calls():

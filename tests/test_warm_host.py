@@ -13,21 +13,13 @@ from pathlib import Path
 import numpy as np
 import pytest
 import warm_newton as wn
+from host_helpers import E_ARG
+from host_helpers import bare_controller as _bare_controller
+from host_helpers import binding as _binding
 
 ROOT = Path(__file__).resolve().parents[1]
 HEADER = ROOT / "include" / "mpcqp.h"
 RESOURCES = ROOT / "build" / "kernel_resources.json"
-E_ARG = -1
-
-
-def _binding():
-    import __graft_entry__ as g
-
-    if not g.LIB.exists():
-        g.build_library()
-    from mpcqp import _lib
-
-    return _lib
 
 
 def test_header_declares_and_library_exports_the_warm_calls():
@@ -131,19 +123,6 @@ def test_shifted_guess_layout():
     U = np.arange(8.0).reshape(2, 4)
     np.testing.assert_array_equal(wn.shifted(U), [[1, 2, 3, 3], [5, 6, 7, 7]])
     np.testing.assert_array_equal(wn.shifted(U[:, :1]), U[:, :1])  # N = 1: nothing to shift
-
-
-def _bare_controller(N=10, max_batch=8, num_classes=0):
-    """A controller object without a workspace (no device here): what the argument checks read."""
-    import torch
-
-    from mpcqp.control.mpc_controller import BatchedMPCController
-
-    c = object.__new__(BatchedMPCController)
-    c._torch = torch
-    c.device = torch.device("cpu")
-    c.horizon, c.max_batch, c.num_classes = N, max_batch, num_classes
-    return c
 
 
 def test_solve_batch_guess_argument_checks():
