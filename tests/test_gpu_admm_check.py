@@ -22,10 +22,10 @@ from __future__ import annotations
 
 import numpy as np
 import pytest
+from gpu_helpers import REL_TOL, base_params, rel, solve
 
 pytestmark = pytest.mark.gpu
 
-REL_TOL = 1e-8  # tests/test_gpu_parity.py, against the same oracle
 # an unpolished ADMM iterate against the restatement's (tests/test_gpu_parity.py: the iterate is only
 # eps = 1e-3 accurate and ~100 iterations amplify the rounding of tree vs sequential sums to ~1e-6)
 REL_TOL_UNPOLISHED = 1e-4
@@ -33,10 +33,6 @@ B = 256
 PAIR_MAX = 15  # two QPs per wave up to this horizon
 
 _cache: dict = {}
-
-
-def _rel(a, b):
-    return float(np.abs(a - b).max() / max(1.0, np.abs(b).max()))
 
 
 def _pairings(N):
@@ -47,12 +43,11 @@ def _restatement(N, **settings):
     """The batch and the C restatement's result for it, computed once per (N, settings)."""
     import cpu_solver
     from mpcqp import scenarios
-    from mpcqp.config import MPCConfig
 
     key = (N, tuple(sorted(settings.items())))
     if key not in _cache:
         batch = scenarios.config3(B, horizon=N)
-        params = MPCConfig(horizon=N).to_parameters(0.8)
+        params = base_params(N)
         cpu = cpu_solver.cpu_solve(params, batch.x0, batch.ref, batch.u_prev, **settings)
         for v in cpu.values():
             if isinstance(v, np.ndarray):
@@ -61,26 +56,14 @@ def _restatement(N, **settings):
     return _cache[key]
 
 
-def _solve(params, batch, pairing, **settings):
-    import torch
-    from mpcqp.control.mpc_controller import BatchedMPCController
-
-    ctrl = BatchedMPCController(params, batch.size, device="cuda:0", pairing=pairing, **settings)
-    sol = ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev)
-    torch.cuda.synchronize()
-    out = {k: getattr(sol, k).cpu().numpy().copy() for k in sol._fields}
-    ctrl.close()
-    return out
-
-
 def _assert_same(out, cpu, what):
     same = (out["iters"] == cpu["iters"]).all(axis=1)
     print(f"{what}: counters equal on {int(same.sum())} of {len(same)} QPs, "
-          f"status equal on {int((out['status'] == cpu['status']).sum())}, rel U {_rel(out['U'], cpu['U']):.2e}")
+          f"status equal on {int((out['status'] == cpu['status']).sum())}, rel U {rel(out['U'], cpu['U']):.2e}")
     assert same.all(), f"{what}: QPs {np.flatnonzero(~same)[:10]} disagree on the counters"
     assert np.array_equal(out["status"], cpu["status"]), what
     assert np.array_equal(out["active"], cpu["active"]), what
-    assert _rel(out["U"], cpu["U"]) <= REL_TOL, what
+    assert rel(out["U"], cpu["U"]) <= REL_TOL, what
 
 
 def _assert_unpolished_rule(out, cpu, what, polished_exact):
@@ -93,8 +76,8 @@ def _assert_unpolished_rule(out, cpu, what, polished_exact):
     if polished_exact:  # solved = converged and polished: the exact optimum
         sel = agree & (cpu["status"] == 1)
         assert np.array_equal(out["active"][sel], cpu["active"][sel]), what
-        assert _rel(out["U"][sel], cpu["U"][sel]) <= REL_TOL, what
-    assert _rel(out["U"][agree], cpu["U"][agree]) <= REL_TOL_UNPOLISHED, what
+        assert rel(out["U"][sel], cpu["U"][sel]) <= REL_TOL, what
+    assert rel(out["U"][agree], cpu["U"][agree]) <= REL_TOL_UNPOLISHED, what
 
 
 @pytest.mark.parametrize("N", [2, 8, 9, 16, 17, 20, 24, 32])
@@ -102,7 +85,7 @@ def test_check_default_settings(cuda, N):
     batch, params, cpu = _restatement(N)
     assert (cpu["status"] == 1).all()
     for pairing in _pairings(N):
-        _assert_same(_solve(params, batch, pairing), cpu, f"N={N} pairing={pairing}")
+        _assert_same(solve(params, batch, pairing=pairing), cpu, f"N={N} pairing={pairing}")
 
 
 @pytest.mark.parametrize("N", [9, 20])
@@ -115,7 +98,7 @@ def test_check_adaptive_rho_refactorizes(cuda, N, rho, share):
     print(f"N={N} rho={rho}: {refac:.0%} of the restatement's QPs factorize twice or more in ADMM")
     assert refac >= share
     for pairing in _pairings(N):
-        _assert_same(_solve(params, batch, pairing, rho=rho), cpu, f"N={N} rho={rho} pairing={pairing}")
+        _assert_same(solve(params, batch, pairing=pairing, rho=rho), cpu, f"N={N} rho={rho} pairing={pairing}")
 
 
 @pytest.mark.parametrize("N", [9, 20])
@@ -126,7 +109,7 @@ def test_check_at_max_iter_off_the_grid(cuda, N):
     print(f"N={N} max_iter=40: restatement statuses {dict(zip(st.tolist(), cnt.tolist()))}")
     assert int((cpu["status"] == 2).sum()) >= 20
     for pairing in _pairings(N):
-        _assert_unpolished_rule(_solve(params, batch, pairing, max_iter=40), cpu,
+        _assert_unpolished_rule(solve(params, batch, pairing=pairing, max_iter=40), cpu,
                                 f"N={N} max_iter=40 pairing={pairing}", polished_exact=True)
 
 
@@ -144,5 +127,5 @@ def test_check_without_polish(cuda, N, settings):
         assert (cpu["status"] == 1).all()
         assert int(checks.max()) >= 4 and int((checks >= 2).sum()) >= 64
     for pairing in _pairings(N):
-        _assert_unpolished_rule(_solve(params, batch, pairing, **settings), cpu,
+        _assert_unpolished_rule(solve(params, batch, pairing=pairing, **settings), cpu,
                                 f"N={N} {settings} pairing={pairing}", polished_exact=False)

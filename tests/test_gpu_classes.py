@@ -19,65 +19,32 @@ from __future__ import annotations
 
 import numpy as np
 import pytest
-from param_variants import VARIANTS, resolution, variant
+from gpu_helpers import (BAD_CLASS, E_ARG, E_HORIZON, E_STATE, FAIL_NOMINAL, OUTS, assert_exact, assert_same,
+                         base_params, controller, fleet_tracker, loop_buffers, take, variant_blocks, varied_fleet)
+from param_variants import VARIANTS
 
 pytestmark = pytest.mark.gpu
 
-REL_TOL = 1e-8  # the project's tolerance against the exact oracle (test_gpu_params.py)
-FAIL_NOMINAL = dict(max_iter=1, polish=0, polish_from=0, polish_near=0.0)  # as test_gpu_params.py
-BAD_CLASS = -11
-E_ARG, E_HORIZON, E_STATE = -1, -2, -5
-_OUTS = ("u0", "X", "U", "status", "iters", "active")
-
-
-def _base(N, res=0.8):
-    from mpcqp.config import MPCConfig
-
-    return MPCConfig(horizon=N).to_parameters(res)
-
-
-def _blocks(N):
-    """The nine MPCParameters variants as classes (dt 0.05 / 0.2 and the 14 px wheelbase among them)."""
-    return [variant(_base(N, resolution(name)), name) for name in VARIANTS]
-
-
-def _controller(params, B, **kw):
-    from mpcqp.control.mpc_controller import BatchedMPCController
-
-    return BatchedMPCController(params, B, device="cuda:0", **kw)
-
-
-def _take(sol):
-    import torch
-
-    torch.cuda.synchronize()  # raises if a kernel of the launch faulted
-    return {k: getattr(sol, k).cpu().numpy().copy() for k in _OUTS}
-
 
 def _plain(params, batch, idx, **kw):
-    ctrl = _controller(params, len(idx), **kw)
+    ctrl = controller(params, len(idx), **kw)
     up = None if batch.u_prev is None else batch.u_prev[idx]
-    out = _take(ctrl.solve_batch(batch.x0[idx], batch.ref[idx], up))
+    out = take(ctrl.solve_batch(batch.x0[idx], batch.ref[idx], up))
     ctrl.close()
     return out
 
 
 def _mixed(base, plist, cls, batch, idx=None, *, class_settings=None, class_method=None, **kw):
     idx = np.arange(batch.size) if idx is None else idx
-    ctrl = _controller(base, len(idx), **kw)
+    ctrl = controller(base, len(idx), **kw)
     ctrl.set_classes(plist, class_settings, method=class_method)
-    out = _take(ctrl.solve_batch(batch.x0[idx], batch.ref[idx], batch.u_prev[idx], classes=np.asarray(cls)[idx]))
+    out = take(ctrl.solve_batch(batch.x0[idx], batch.ref[idx], batch.u_prev[idx], classes=np.asarray(cls)[idx]))
     ctrl.close()
     return out
 
 
 def _assert_rows_equal(mixed, rows, plain, what):
-    for k in _OUTS:
-        np.testing.assert_array_equal(mixed[k][rows], plain[k], err_msg=f"{what}: {k}")
-
-
-def _rel(a, b):
-    return float(np.abs(a - b).max() / max(1.0, np.abs(b).max()))
+    assert_same({k: mixed[k][rows] for k in OUTS}, plain, what)
 
 
 # ---------------------------------------------------------------------- 1. oracle parity
@@ -88,19 +55,17 @@ def test_mixed_batch_matches_exact_oracle_per_class(cuda, N):
     import mpc_oracle as mo
     from mpcqp import scenarios
 
-    plist = _blocks(N)
+    plist = variant_blocks(N)
     batch = scenarios.config3(48, horizon=N, seed=1000 + N)
     cls = np.arange(batch.size) % len(plist)
-    out = _mixed(_base(N), plist, cls, batch)
+    out = _mixed(base_params(N), plist, cls, batch)
     assert (out["status"] == 1).all(), np.unique(out["status"], return_counts=True)
     n_active = 0
     for b in range(batch.size):
         ex = mo.solve_exact(plist[cls[b]], batch.x0[b], batch.ref[b], batch.u_prev[b])
         assert ex.converged
-        e = max(_rel(out["U"][b], ex.Umat), _rel(out["X"][b], ex.X), _rel(out["u0"][b], ex.Umat[:, 0]))
+        e = assert_exact(out, b, ex, f"N={N} ({VARIANTS[cls[b]]})")
         print(f"N={N} QP {b} class {VARIANTS[cls[b]]}: rel err {e:.3e}")
-        assert e <= REL_TOL, f"N={N} QP {b} ({VARIANTS[cls[b]]}): rel err {e:.3e}"
-        assert np.array_equal(out["active"][b], ex.active), f"N={N} QP {b} ({VARIANTS[cls[b]]}): active set differs"
         n_active += int((ex.active != 0).any())
     assert n_active > 0
 
@@ -117,10 +82,10 @@ def test_mixed_launch_equals_homogeneous_launches_bitwise(cuda, N, B, kw):
     plain side runs two QPs per wave, the mixed launch never does)."""
     from mpcqp import scenarios
 
-    plist = _blocks(N)
+    plist = variant_blocks(N)
     batch = scenarios.config3(B, horizon=N, seed=2000 + N)
     cls = np.arange(B) % len(plist)
-    mixed = _mixed(_base(N), plist, cls, batch, **kw)
+    mixed = _mixed(base_params(N), plist, cls, batch, **kw)
     for c, p in enumerate(plist):
         rows = np.flatnonzero(cls == c)
         _assert_rows_equal(mixed, rows, _plain(p, batch, rows, **kw), f"N={N} class {VARIANTS[c]}")
@@ -136,12 +101,12 @@ def test_one_class_equals_plain_solve_batch_bitwise(cuda, N):
 
     B = 18 if N <= 64 else 9
     batch = scenarios.config3(B, horizon=N, seed=3000 + N)
-    p = _base(N)
-    ctrl = _controller(p, B)
-    plain = _take(ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev))
+    p = base_params(N)
+    ctrl = controller(p, B)
+    plain = take(ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev))
     ctrl.set_classes([p])
     cls = torch.zeros(B, dtype=torch.int32, device="cuda:0")
-    one = _take(ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev, classes=cls))
+    one = take(ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev, classes=cls))
     ctrl.close()
     _assert_rows_equal(one, np.arange(B), plain, f"N={N} K=1")
     assert (plain["status"] == 1).any(), plain["status"]
@@ -154,7 +119,7 @@ def test_classes_differ_in_solver_settings(cuda):
     from mpcqp import scenarios
 
     N, B = 20, 24
-    p = _base(N)
+    p = base_params(N)
     batch = scenarios.config3(B, horizon=N, seed=41)
     cls = np.arange(B) % 2
     out = _mixed(p, [p, p], cls, batch, class_settings=[{}, FAIL_NOMINAL])
@@ -170,7 +135,7 @@ def test_classes_differ_in_method(cuda):
     from mpcqp import scenarios
 
     N, B = 20, 24
-    p = _base(N)
+    p = base_params(N)
     batch = scenarios.config3(B, horizon=N, seed=42)
     cls = np.arange(B) % 2
     out = _mixed(p, [p, p], cls, batch, class_method=["admm", "newton"])
@@ -190,7 +155,7 @@ def test_bad_class_indices_are_reported_per_qp(cuda, N):
     from mpcqp import scenarios
 
     B = 12
-    plist = _blocks(N)[:4]
+    plist = variant_blocks(N)[:4]
     K = len(plist)
     batch = scenarios.config3(B, horizon=N, seed=4000 + N)
     cls = np.arange(B) % K
@@ -198,11 +163,11 @@ def test_bad_class_indices_are_reported_per_qp(cuda, N):
     for b, c in bad.items():
         cls[b] = c
     good = np.array([b for b in range(B) if b not in bad])
-    ctrl = _controller(_base(N), B)
+    ctrl = controller(base_params(N), B)
     ctrl.set_classes(plist)
     for buf, fill in ((ctrl._u0, 7.25), (ctrl._X, 7.25), (ctrl._U, 7.25), (ctrl._active, 77), (ctrl._iters, 77)):
         buf.fill_(fill)
-    out = _take(ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev, classes=cls))  # returns, and the sync is clean
+    out = take(ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev, classes=cls))  # returns, and the sync is clean
     ctrl.close()
     rows = np.array(sorted(bad))
     assert (out["status"][rows] == BAD_CLASS).all(), out["status"]
@@ -210,7 +175,7 @@ def test_bad_class_indices_are_reported_per_qp(cuda, N):
     for k, fill in (("u0", 7.25), ("X", 7.25), ("U", 7.25), ("active", 77)):
         assert (out[k][rows] == fill).all(), f"{k} of a bad-class QP was written"
     assert (out["status"][good] == 1).any(), out["status"]
-    _assert_rows_equal(out, good, _mixed(_base(N), plist, cls, batch, good), f"N={N} valid QPs")
+    _assert_rows_equal(out, good, _mixed(base_params(N), plist, cls, batch, good), f"N={N} valid QPs")
 
 
 # ---------------------------------------------------------------------- 5. state rules
@@ -219,10 +184,10 @@ def test_class_state_rules(cuda):
     from mpcqp import _lib, scenarios
 
     N, B = 12, 10
-    p = _base(N)
-    plist = _blocks(N)[:3]
+    p = base_params(N)
+    plist = variant_blocks(N)[:3]
     batch = scenarios.config3(B, horizon=N, seed=5)
-    ctrl = _controller(p, B)
+    ctrl = controller(p, B)
     L, ws = ctrl._L, ctrl._ws
     x0, ref, up = (torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0") for a in (batch.x0, batch.ref, batch.u_prev))
     cls = torch.from_numpy((np.arange(B) % 3).astype(np.int32)).to("cuda:0")
@@ -240,7 +205,7 @@ def test_class_state_rules(cuda):
     with pytest.raises(ValueError):
         ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev, classes=np.zeros(B, np.int32))
     # a block with another horizon / with debug_state is refused and leaves no table behind
-    wrong = _lib.class_table([_base(N + 1)])
+    wrong = _lib.class_table([base_params(N + 1)])
     assert L.mpcqp_set_classes(ws, 1, wrong) == E_HORIZON
     dbg = _lib.class_table(plist)
     dbg[1].debug_state = 1
@@ -253,7 +218,7 @@ def test_class_state_rules(cuda):
     ctrl.set_classes(plist)
     assert solve() == E_STATE
     assert build_mixed() == 0 and solve() == 0
-    mixed = _take(ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev, classes=cls))
+    mixed = take(ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev, classes=cls))
     for c in range(3):
         rows = np.flatnonzero(np.arange(B) % 3 == c)
         _assert_rows_equal(mixed, rows, _plain(plist[c], batch, rows), f"class {c}")
@@ -263,14 +228,14 @@ def test_class_state_rules(cuda):
     assert solve() == E_STATE
     assert build_mixed() == 0 and solve() == 0
     # a plain build after a mixed one solves under the workspace's own block
-    plain = _take(ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev))
+    plain = take(ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev))
     _assert_rows_equal(plain, np.arange(B), _plain(p, batch, np.arange(B)), "plain after mixed")
     # dropping the table
     ctrl.set_classes(None)
     assert ctrl.num_classes == 0 and build_mixed() == E_STATE
     with pytest.raises(ValueError):
         ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev, classes=cls)
-    again = _take(ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev))
+    again = take(ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev))
     _assert_rows_equal(again, np.arange(B), plain, "plain after the table is dropped")
     torch.cuda.synchronize()
     ctrl.close()
@@ -292,11 +257,10 @@ def test_solve_without_a_valid_build_is_refused(cuda, golden):
 
     import torch
     from mpcqp import scenarios
-    from test_gpu_fleet import _tracker, _varied_fleet
 
     N, V = 3, 2
-    g, paths, starts, goals = _varied_fleet(golden, V)
-    ft = _tracker(N, V, 128, 4, use_graph=False)
+    g, paths, starts, goals = varied_fleet(golden, V, seed=5)
+    ft = fleet_tracker(N, V, 128, 4, use_graph=False)
     ctrl = ft._nominal
     L, ws = ctrl._L, ctrl._ws
     for name, fill in _FILLS:
@@ -324,24 +288,23 @@ def test_fused_loop_after_a_mixed_build_equals_fresh_workspaces(cuda, golden):
     bit, and mpcqp_solve afterwards needs a new build."""
     import torch
     from mpcqp import scenarios
-    from test_gpu_fleet import _tracker, _varied_fleet
 
     N, V, steps = 3, 3, 4
-    g, paths, starts, goals = _varied_fleet(golden, V)
+    g, paths, starts, goals = varied_fleet(golden, V, seed=5)
     batch = scenarios.config3(V, horizon=N, seed=9)
     bufs = []
     for mixed_first in (False, True):
-        ft = _tracker(N, V, 128, steps, fused=True)
+        ft = fleet_tracker(N, V, 128, steps, fused=True)
         for c in (ft._nominal, ft._relaxed):
             c.set_pairing("on")
         if mixed_first:
-            ft._nominal.set_classes(_blocks(N)[:2])
-            out = _take(ft._nominal.solve_batch(batch.x0, batch.ref, batch.u_prev, classes=np.arange(V) % 2))
+            ft._nominal.set_classes(variant_blocks(N)[:2])
+            out = take(ft._nominal.solve_batch(batch.x0, batch.ref, batch.u_prev, classes=np.arange(V) % 2))
             assert (out["status"] != BAD_CLASS).all() and (out["status"] == 1).any(), out["status"]
         ft.reset_from_plans(paths, starts, goals)
         ft.step(steps)
         torch.cuda.synchronize()
-        bufs.append({k: t.cpu().numpy().copy() for k, t in ft.buffers().items()})
+        bufs.append(loop_buffers(ft, tuple(ft.buffers())))
         assert _raw_solve(ft._nominal, V) == E_STATE
         ft.close()
     assert (bufs[0]["steps"] > 0).any(), bufs[0]["steps"]  # the loop stepped

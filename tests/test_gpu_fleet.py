@@ -17,32 +17,9 @@ from types import SimpleNamespace
 
 import numpy as np
 import pytest
+from gpu_helpers import ATOL, E_HORIZON, E_STATE, LOOP_BUFFERS, default_plan, fleet_tracker, loop_buffers, varied_fleet
 
 pytestmark = pytest.mark.gpu
-
-ATOL = 1e-7
-
-
-def _default_plan(golden):
-    g = golden("default_plan.npz")
-    path = [tuple(map(float, p)) for p in g["path"]]
-    return g, path
-
-
-def _branches(golden):
-    """The RRT* branch splines of the BASELINE config-3 generator (branches.npz)."""
-    br = golden("branches.npz")
-    off = br["spline_off"]
-    return [br["spline"][off[i]:off[i + 1]] for i in range(len(off) - 1)]
-
-
-def _tracker(N, V, M, sim_steps, map_resolution=0.8, use_graph=True, fused=False, **settings):
-    from mpcqp.config import MPCConfig
-    from mpcqp.pipeline.fleet import FleetTracker
-
-    mpc = MPCConfig(horizon=N, sim_steps=sim_steps)
-    return FleetTracker(mpc, map_resolution=map_resolution, max_vehicles=V, max_ref_len=M, device="cuda:0",
-                        use_graph=use_graph, fused=fused, **settings)
 
 
 @pytest.mark.parametrize("fused", [False, True])
@@ -50,10 +27,10 @@ def _tracker(N, V, M, sim_steps, map_resolution=0.8, use_graph=True, fused=False
 def test_fleet_reproduces_reference_closed_loop(cuda, golden, N, sim_steps, fused):
     from mpcqp import _lib
 
-    g, path = _default_plan(golden)
+    g, path = default_plan(golden)
     loop = golden("closed_loop.npz")
     V = 16
-    ft = _tracker(N, V, 64, sim_steps, float(g["map_resolution"]), fused=fused)
+    ft = fleet_tracker(N, V, 64, sim_steps, float(g["map_resolution"]), fused=fused)
     ft.reset_from_plans([path] * V, np.tile(g["start"], (V, 1)), np.tile(g["goal"], (V, 1)))
     res = ft.run()
     ref_states = loop[f"N{N}_states"]
@@ -68,23 +45,13 @@ def test_fleet_reproduces_reference_closed_loop(cuda, golden, N, sim_steps, fuse
     ft.close()
 
 
-def _varied_fleet(golden, V, seed=5):
-    g, path = _default_plan(golden)
-    paths = _branches(golden) + [np.asarray(path)]
-    rng = np.random.default_rng(seed)
-    chosen = [paths[i % len(paths)] for i in range(V)]
-    starts = np.array([p[0] for p in chosen]) + rng.uniform(-3, 3, size=(V, 2))
-    goals = np.array([p[-1] for p in chosen])
-    return g, chosen, starts, goals
-
-
 def test_fleet_matches_exact_oracle_loop(cuda, golden):
     import mpc_oracle as mo
     from mpcqp.control.ref_builder import build_reference
 
     N, steps = 15, 40
-    g, paths, starts, goals = _varied_fleet(golden, 4)
-    ft = _tracker(N, 4, 128, steps, float(g["map_resolution"]))
+    g, paths, starts, goals = varied_fleet(golden, 4, seed=5)
+    ft = fleet_tracker(N, 4, 128, steps, float(g["map_resolution"]))
     refs = ft.reset_from_plans(paths, starts, goals)
     res = ft.run()
     op = mo.default_params(N, float(g["map_resolution"]))
@@ -106,8 +73,8 @@ def test_fleet_matches_host_tracker(cuda, golden):
     from mpcqp.pipeline.control_stage import TrajectoryTracker
 
     N, steps, V = 20, 60, 13
-    g, paths, starts, goals = _varied_fleet(golden, V, seed=11)
-    ft = _tracker(N, 32, 128, steps, 0.8)
+    g, paths, starts, goals = varied_fleet(golden, V, seed=11)
+    ft = fleet_tracker(N, 32, 128, steps, 0.8)
     ft.reset_from_plans(paths, starts, goals)
     res = ft.run(check_every=7)
     tracker = TrajectoryTracker(MPCConfig(horizon=N, sim_steps=steps), VizConfig())
@@ -124,10 +91,10 @@ def test_fleet_matches_host_tracker(cuda, golden):
 
 def test_graph_and_stream_paths_agree_bitwise(cuda, golden):
     N, steps, V = 20, 30, 40
-    g, paths, starts, goals = _varied_fleet(golden, V, seed=3)
+    g, paths, starts, goals = varied_fleet(golden, V, seed=3)
     out = []
     for use_graph in (True, False):
-        ft = _tracker(N, V, 128, steps, use_graph=use_graph)
+        ft = fleet_tracker(N, V, 128, steps, use_graph=use_graph)
         ft.reset_from_plans(paths, starts, goals)
         out.append(ft.run(check_every=9))
         ft.close()
@@ -144,8 +111,8 @@ def test_unsolvable_vehicle_aborts_alone(cuda, golden):
     from mpcqp import _lib
 
     N, steps, V = 10, 20, 6
-    g, path = _default_plan(golden)
-    ft = _tracker(N, V, 64, steps, float(g["map_resolution"]))
+    g, path = default_plan(golden)
+    ft = fleet_tracker(N, V, 64, steps, float(g["map_resolution"]))
     ft.reset_from_plans([path] * V, np.tile(g["start"], (V, 1)), np.tile(g["goal"], (V, 1)))
     ft.buffers()["state"][2, 0] = float("nan")
     ft.step(1)
@@ -169,9 +136,9 @@ def test_fleet_large_batch_properties(cuda, golden):
     import mpc_oracle as mo
 
     N, steps, V = 20, 12, 4096
-    g, paths, starts, goals = _varied_fleet(golden, 13, seed=21)
+    g, paths, starts, goals = varied_fleet(golden, 13, seed=21)
     idx = np.arange(V) % 13
-    ft = _tracker(N, V, 128, steps)
+    ft = fleet_tracker(N, V, 128, steps)
     ft.reset_from_plans([paths[i] for i in idx], starts[idx], goals[idx])
     res = ft.run()
     b = ft.buffers()
@@ -190,26 +157,21 @@ def test_fleet_large_batch_properties(cuda, golden):
     ft.close()
 
 
-# every buffer the loop owns (the masks are scratch: the stepped path clears them for vehicles that
-# no longer run, the fused loop leaves each vehicle's last-step masks)
-_LOOP_BUFFERS = ("state", "u_prev", "path_idx", "phase", "steps", "trace", "u_trace", "X", "status", "u0")
-
-
 @pytest.mark.parametrize("N,V,steps,seed", [(10, 40, 60, 3), (20, 300, 45, 7), (24, 64, 30, 9), (30, 64, 30, 13)])
 def test_fused_loop_equals_stepped_loop_bitwise(cuda, golden, N, V, steps, seed):
     """mpcqp_fleet_loop (one launch, k_fleet_loop) == mpcqp_fleet_run (graph-replayed steps), every
     output buffer bit for bit: N = 10 / 20 keep the model block in LDS, N = 24 / 30 re-derive it
     from the window for the outputs (packed Pbar), N = 30 at the register limit."""
-    g, paths, starts, goals = _varied_fleet(golden, V, seed=seed)
+    g, paths, starts, goals = varied_fleet(golden, V, seed=seed)
     bufs = []
     for fused in (False, True):
-        ft = _tracker(N, V, 128, steps, fused=fused)
+        ft = fleet_tracker(N, V, 128, steps, fused=fused)
         ft.reset_from_plans(paths, starts, goals)
         res = ft.run()
-        bufs.append({k: ft.buffers()[k].cpu().numpy().copy() for k in _LOOP_BUFFERS})
+        bufs.append(loop_buffers(ft))
         ft.close()
     a, b = bufs
-    for k in _LOOP_BUFFERS:
+    for k in LOOP_BUFFERS:
         np.testing.assert_array_equal(a[k], b[k], err_msg=k)
     assert (res.phase != 0).all() or (res.steps == steps).all()
 
@@ -218,17 +180,17 @@ def test_fused_loop_partial_runs_and_resume(cuda, golden):
     """steps < needed: the fused loop stops every vehicle after that many steps and a second call
     resumes from the device state -- the same as stepping."""
     N, V = 15, 24
-    g, paths, starts, goals = _varied_fleet(golden, V, seed=17)
+    g, paths, starts, goals = varied_fleet(golden, V, seed=17)
     out = []
     for fused in (False, True):
-        ft = _tracker(N, V, 128, 80, fused=fused)
+        ft = fleet_tracker(N, V, 128, 80, fused=fused)
         ft.reset_from_plans(paths, starts, goals)
         ft.step(7)
         ft.step(11)
         res = ft.run()
-        out.append((res, {k: ft.buffers()[k].cpu().numpy().copy() for k in _LOOP_BUFFERS}))
+        out.append((res, loop_buffers(ft)))
         ft.close()
-    for k in _LOOP_BUFFERS:
+    for k in LOOP_BUFFERS:
         np.testing.assert_array_equal(out[0][1][k], out[1][1][k], err_msg=k)
 
 
@@ -236,8 +198,8 @@ def test_fused_loop_unsolvable_vehicle_aborts_alone(cuda, golden):
     from mpcqp import _lib
 
     N, steps, V = 10, 20, 6
-    g, path = _default_plan(golden)
-    ft = _tracker(N, V, 64, steps, float(g["map_resolution"]), fused=True)
+    g, path = default_plan(golden)
+    ft = fleet_tracker(N, V, 64, steps, float(g["map_resolution"]), fused=True)
     ft.reset_from_plans([path] * V, np.tile(g["start"], (V, 1)), np.tile(g["goal"], (V, 1)))
     ft.buffers()["state"][2, 0] = float("nan")
     res = ft.run()
@@ -257,15 +219,15 @@ def test_fused_loop_falls_back_past_one_wave(cuda, golden):
     """Horizons past the one-wave kernel (N = 40, mid kernel) run mpcqp_fleet_loop through the
     stepped graph path: the same results as mpcqp_fleet_run."""
     N, V, steps = 40, 8, 12
-    g, paths, starts, goals = _varied_fleet(golden, V, seed=23)
+    g, paths, starts, goals = varied_fleet(golden, V, seed=23)
     bufs = []
     for fused in (False, True):
-        ft = _tracker(N, V, 160, steps, fused=fused)
+        ft = fleet_tracker(N, V, 160, steps, fused=fused)
         ft.reset_from_plans(paths, starts, goals)
         ft.run()
-        bufs.append({k: ft.buffers()[k].cpu().numpy().copy() for k in _LOOP_BUFFERS})
+        bufs.append(loop_buffers(ft))
         ft.close()
-    for k in _LOOP_BUFFERS:
+    for k in LOOP_BUFFERS:
         np.testing.assert_array_equal(bufs[0][k], bufs[1][k], err_msg=k)
 
 
@@ -277,16 +239,16 @@ def test_fused_loop_dispatch_order_past_the_wave_slots(cuda, golden):
     props = torch.cuda.get_device_properties(0)
     N, steps = 10, 25
     V = 8 * props.multi_processor_count + 300
-    g, paths, starts, goals = _varied_fleet(golden, 13, seed=29)
+    g, paths, starts, goals = varied_fleet(golden, 13, seed=29)
     idx = np.arange(V) % 13
     bufs = []
     for fused in (False, True):
-        ft = _tracker(N, V, 128, steps, fused=fused)
+        ft = fleet_tracker(N, V, 128, steps, fused=fused)
         ft.reset_from_plans([paths[i] for i in idx], starts[idx], goals[idx])
         ft.run()
-        bufs.append({k: ft.buffers()[k].cpu().numpy().copy() for k in _LOOP_BUFFERS})
+        bufs.append(loop_buffers(ft))
         ft.close()
-    for k in _LOOP_BUFFERS:
+    for k in LOOP_BUFFERS:
         np.testing.assert_array_equal(bufs[0][k], bufs[1][k], err_msg=k)
 
 
@@ -300,9 +262,8 @@ def test_fused_loop_calls_that_enqueue_nothing_keep_the_build(cuda, golden, entr
 
     import torch
 
-    E_HORIZON, E_STATE = -2, -5
     N = V = 3
-    _, paths, starts, goals = _varied_fleet(golden, V, seed=37)
+    _, paths, starts, goals = varied_fleet(golden, V, seed=37)
     x0 = np.tile([10.0, 10.0, 0.0, 5.0], (V, 1))
     ref = np.tile(np.array([[10.0 + 1.5 * k, 10.0, 0.0, 15.0] for k in range(N + 1)]), (V, 1, 1))
 
@@ -328,7 +289,7 @@ def test_fused_loop_calls_that_enqueue_nothing_keep_the_build(cuda, golden, entr
 
     modes = [({}, 0)] + ([(dict(reproducible=1), E_HORIZON)] if entry != "plain" else [])
     for settings, refused in modes:
-        ft = _tracker(N, V, 128, 12, fused=True, **settings)
+        ft = fleet_tracker(N, V, 128, 12, fused=True, **settings)
         if entry == "mixed":
             ft.set_classes([ft.params, ft.params])
         ft.reset_from_plans(paths, starts, goals)

@@ -5,7 +5,7 @@ The claim: vehicle v of a mixed fleet gets, bit for bit, the buffers of a homoge
 (``mpcqp_fleet_loop``) under its class's nominal and relaxed blocks -- so every comparison with a
 homogeneous fleet is ``assert_array_equal`` over every buffer row.  Against the exact oracle's loop
 the states agree to the 1e-7 px of test_gpu_fleet.py.  Fleets are those of
-``test_gpu_fleet._varied_fleet``, the blocks come from ``param_variants``, and each vehicle's
+``gpu_helpers.varied_fleet``, the blocks come from ``param_variants``, and each vehicle's
 reference is built with its class's ``dt``.
 """
 from __future__ import annotations
@@ -14,60 +14,17 @@ import ctypes
 
 import numpy as np
 import pytest
-from param_variants import resolution, variant
+from gpu_helpers import (ATOL, E_HORIZON, E_STATE, FAIL_NOMINAL, LOOP_BUFFERS_MASK, TWO_SLOT, assert_same,
+                         fleet_tracker, oracle_variant_params, snap, variant_blocks, variant_params, varied_fleet)
 
 pytestmark = pytest.mark.gpu
 
-ATOL = 1e-7  # px, as test_gpu_fleet.py
 BLOCKS = ["default", "dt_0.05", "dt_0.2", "wheelbase_14px", "tight_bounds", "q_nondiag"]
-FAIL_NOMINAL = dict(max_iter=1, polish=0, polish_from=0, polish_near=0.0)  # as test_gpu_params.py
-E_HORIZON, E_STATE = -2, -5
 M_REF = 128  # reference rows per vehicle (the longest of these plans has 45, at every dt used here)
-# per-vehicle buffers; status / u0 / mask hold a nominal and a relaxed slot: vehicles along axis 1
-KEYS = ["state", "u_prev", "path_idx", "phase", "steps", "trace", "u_trace", "X", "status", "u0", "mask"]
-TWO_SLOT = ("status", "u0", "mask")
 
 
-def _block(name, N):
-    from mpcqp.config import MPCConfig
-
-    if name == "default":
-        return MPCConfig(horizon=N).to_parameters(0.8)
-    return variant(MPCConfig(horizon=N).to_parameters(resolution(name)), name)
-
-
-def _oracle_block(name, N):
-    import mpc_oracle as mo
-
-    if name == "default":
-        return mo.default_params(N, 0.8)
-    return variant(mo.default_params(N, resolution(name)), name)
-
-
-def _tracker(N, V, max_steps, params=None, **settings):
-    from mpcqp.config import MPCConfig
-    from mpcqp.pipeline.fleet import FleetTracker
-
-    return FleetTracker(MPCConfig(horizon=N, sim_steps=max_steps), map_resolution=0.8, max_vehicles=V,
-                        max_ref_len=M_REF, device="cuda:0", fused=True, params=params, **settings)
-
-
-def _snap(ft):
-    import torch
-
-    torch.cuda.synchronize()
-    V = ft.vehicles
-    b = ft.buffers()
-    return {k: (b[k][:, :V] if k in TWO_SLOT else b[k][:V]).cpu().numpy().copy() for k in KEYS}
-
-
-def _rows(snap, idx):
-    return {k: (a[:, idx] if k in TWO_SLOT else a[idx]) for k, a in snap.items()}
-
-
-def _assert_same(got, want, what):
-    for k in KEYS:
-        np.testing.assert_array_equal(got[k], want[k], err_msg=f"{what}: buffer {k}")
+def _rows(bufs, idx):
+    return {k: (a[:, idx] if k in TWO_SLOT else a[idx]) for k, a in bufs.items()}
 
 
 def _sub(seq, idx):
@@ -76,11 +33,11 @@ def _sub(seq, idx):
 
 def _homogeneous(N, max_steps, block, paths, starts, goals, steps=None, **settings):
     """The buffers of a homogeneous fused fleet under ``block`` (reference at the block's dt)."""
-    ft = _tracker(N, len(paths), max_steps, params=block, **settings)
+    ft = fleet_tracker(N, len(paths), M_REF, max_steps, fused=True, params=block, **settings)
     ft.reset_from_plans(paths, starts, goals)
     for k in ([max_steps] if steps is None else steps):
         ft.step(k)
-    out = _snap(ft)
+    out = snap(ft)
     ft.close()
     return out
 
@@ -91,7 +48,7 @@ def _check_against_per_class_fleets(got, cls, N, max_steps, blocks, paths, start
         assert len(idx), f"class {c} has no vehicle"
         kw = per_class[c] if per_class else {}
         want = _homogeneous(N, max_steps, block, _sub(paths, idx), starts[idx], goals[idx], steps, **kw)
-        _assert_same(_rows(got, idx), want, f"class {c}")
+        assert_same(_rows(got, idx), want, f"class {c}", LOOP_BUFFERS_MASK)
 
 
 @pytest.mark.parametrize("N", [3, 10, 20, 32])
@@ -99,17 +56,16 @@ def test_mixed_fleet_equals_homogeneous_fleets_bitwise(cuda, golden, N):
     """18 vehicles, six classes (two dt's off the default, another wheelbase, tighter bounds, a
     non-diagonal Q), 25 steps; N = 10 is a horizon at which homogeneous loops may pair."""
     from mpcqp import _lib
-    from test_gpu_fleet import _varied_fleet
 
     V, steps = 18, 25
-    _, paths, starts, goals = _varied_fleet(golden, V)
-    blocks = [_block(name, N) for name in BLOCKS]
+    _, paths, starts, goals = varied_fleet(golden, V, seed=5)
+    blocks = variant_blocks(N, BLOCKS)
     cls = np.arange(V) % len(blocks)
-    ft = _tracker(N, V, steps)
+    ft = fleet_tracker(N, V, M_REF, steps, fused=True)
     ft.set_classes(blocks)
     ft.reset_from_plans(paths, starts, goals, classes=cls)
     res = ft.run()
-    got = _snap(ft)
+    got = snap(ft)
     ft.close()
     assert (res.steps > 0).any(), "no vehicle stepped"
     assert np.isin(res.phase, [_lib.FLEET_GOAL, _lib.FLEET_OUT_OF_STEPS]).any(), res.phase
@@ -121,18 +77,17 @@ def test_mixed_fleet_equals_homogeneous_fleets_bitwise(cuda, golden, N):
 def test_one_class_equals_the_plain_loop_bitwise(cuda, golden, N, pairing):
     """K = 1 with the tracker's own block against plain mpcqp_fleet_loop (N = 3: the plain side runs two
     vehicles per wave, the mixed side never does)."""
-    from test_gpu_fleet import _varied_fleet
 
     V, steps = 9, 20
-    _, paths, starts, goals = _varied_fleet(golden, V, seed=7)
-    ft = _tracker(N, V, steps)
+    _, paths, starts, goals = varied_fleet(golden, V, seed=7)
+    ft = fleet_tracker(N, V, M_REF, steps, fused=True)
     ft.set_classes([ft.params])
     ft.reset_from_plans(paths, starts, goals, classes=np.zeros(V, np.int32))
     ft.run()
-    got = _snap(ft)
+    got = snap(ft)
     ft.close()
     want = _homogeneous(N, steps, None, paths, starts, goals, pairing=pairing)
-    _assert_same(got, want, "K = 1")
+    assert_same(got, want, "K = 1", LOOP_BUFFERS_MASK)
 
 
 def test_mixed_fleet_matches_exact_oracle_loop(cuda, golden):
@@ -141,13 +96,12 @@ def test_mixed_fleet_matches_exact_oracle_loop(cuda, golden):
     import mpc_oracle as mo
     from mpcqp import _lib
     from mpcqp.control.ref_builder import build_reference
-    from test_gpu_fleet import _varied_fleet
 
     N, steps, V = 15, 30, 12
-    _, paths, starts, goals = _varied_fleet(golden, V)
-    blocks = [_block(name, N) for name in BLOCKS]
+    _, paths, starts, goals = varied_fleet(golden, V, seed=5)
+    blocks = variant_blocks(N, BLOCKS)
     cls = np.arange(V) % len(blocks)
-    ft = _tracker(N, V, steps)
+    ft = fleet_tracker(N, V, M_REF, steps, fused=True)
     ft.set_classes(blocks)
     refs = ft.reset_from_plans(paths, starts, goals, classes=cls)
     res = ft.run()
@@ -156,7 +110,7 @@ def test_mixed_fleet_matches_exact_oracle_loop(cuda, golden):
     assert (res.phase == _lib.FLEET_GOAL).any() and (res.phase == _lib.FLEET_OUT_OF_STEPS).any(), res.phase
     for v in range(V):
         name = BLOCKS[cls[v]]
-        op = _oracle_block(name, N)
+        op = oracle_variant_params(name, N)
         ref = build_reference(paths[v], 15.0, N, op.dt)
         np.testing.assert_array_equal(refs[v], ref)
         p = paths[v]
@@ -172,17 +126,16 @@ def test_relaxed_retry_per_class(cuda, golden):
     """Class 1's nominal settings fail every QP, so its vehicles take the retry under relaxed block 1
     (another wheelbase than class 0's): a wrong 2c + relax index would show in the bits."""
     from mpcqp import _lib
-    from test_gpu_fleet import _varied_fleet
 
     N, V, max_steps, steps = 10, 8, 50, 5
-    _, paths, starts, goals = _varied_fleet(golden, V, seed=2)
-    blocks = [_block("default", N), _block("wheelbase_14px", N)]
+    _, paths, starts, goals = varied_fleet(golden, V, seed=2)
+    blocks = [variant_params("default", N), variant_params("wheelbase_14px", N)]
     cls = np.array([0, 1, 1, 0, 1, 0, 0, 1])
-    ft = _tracker(N, V, max_steps)
+    ft = fleet_tracker(N, V, M_REF, max_steps, fused=True)
     ft.set_classes(blocks, settings=[{}, FAIL_NOMINAL], relaxed_settings=[{}, {}])
     ft.reset_from_plans(paths, starts, goals, classes=cls)
     ft.step(steps)
-    got = _snap(ft)
+    got = snap(ft)
     ft.close()
     assert (got["phase"] == _lib.FLEET_RUNNING).all(), got["phase"]
     assert (got["steps"] == steps).all()
@@ -196,27 +149,26 @@ def test_relaxed_retry_per_class(cuda, golden):
 def test_bad_class_aborts_that_vehicle_only(cuda, golden):
     import torch
     from mpcqp import _lib
-    from test_gpu_fleet import _varied_fleet
 
     N, V, max_steps, steps = 10, 10, 40, 6
     SENT = -777.0
-    _, paths, starts, goals = _varied_fleet(golden, V, seed=4)
-    blocks = [_block(name, N) for name in ("default", "dt_0.2", "tight_bounds")]
+    _, paths, starts, goals = varied_fleet(golden, V, seed=4)
+    blocks = variant_blocks(N, ("default", "dt_0.2", "tight_bounds"))
     cls = np.array([0, 1, -1, 2, 0, len(blocks), 1, 2**31 - 1, 2, 0], dtype=np.int64)
     bad = np.flatnonzero((cls < 0) | (cls >= len(blocks)))
     good = np.flatnonzero((cls >= 0) & (cls < len(blocks)))
     assert list(bad) == [2, 5, 7]
 
     def run(idx):
-        ft = _tracker(N, len(idx), max_steps)
+        ft = fleet_tracker(N, len(idx), M_REF, max_steps, fused=True)
         ft.set_classes(blocks)
         ft.reset_from_plans(_sub(paths, idx), starts[idx], goals[idx], classes=cls[idx])
         for k in ("trace", "X", "u0"):
             ft.buffers()[k].fill_(SENT)
-        before = _snap(ft)
+        before = snap(ft)
         ft.step(steps)
         torch.cuda.synchronize()  # no fault: an index outside the table was never used
-        after = _snap(ft)
+        after = snap(ft)
         ft.close()
         return before, after
 
@@ -224,7 +176,7 @@ def test_bad_class_aborts_that_vehicle_only(cuda, golden):
     assert (after["phase"][bad] == _lib.FLEET_ABORTED).all(), after["phase"]
     assert (after["status"][0][bad] == _lib.BAD_CLASS).all(), after["status"]
     assert (after["mask"][:, bad] == 0).all()
-    for k in KEYS:  # nothing else of a bad vehicle is written
+    for k in LOOP_BUFFERS_MASK:  # nothing else of a bad vehicle is written
         if k in ("phase", "mask"):
             continue
         a, b = _rows(after, bad)[k], _rows(before, bad)[k]
@@ -235,28 +187,27 @@ def test_bad_class_aborts_that_vehicle_only(cuda, golden):
     # the others ran as without them
     assert (after["steps"][good] == steps).all()
     _, alone = run(good)
-    _assert_same(_rows(after, good), alone, "valid vehicles")
+    assert_same(_rows(after, good), alone, "valid vehicles", LOOP_BUFFERS_MASK)
 
 
 def test_partial_runs_add_up_bitwise(cuda, golden):
     """step(3) then step(4) == step(7): the loop state written back between launches is complete."""
-    from test_gpu_fleet import _varied_fleet
 
     N, V, max_steps = 10, 9, 30
-    _, paths, starts, goals = _varied_fleet(golden, V, seed=9)
-    blocks = [_block(name, N) for name in ("default", "dt_0.05", "q_nondiag")]
+    _, paths, starts, goals = varied_fleet(golden, V, seed=9)
+    blocks = variant_blocks(N, ("default", "dt_0.05", "q_nondiag"))
     cls = np.arange(V) % 3
     out = []
     for parts in ([3, 4], [7]):
-        ft = _tracker(N, V, max_steps)
+        ft = fleet_tracker(N, V, M_REF, max_steps, fused=True)
         ft.set_classes(blocks)
         ft.reset_from_plans(paths, starts, goals, classes=cls)
         for k in parts:
             ft.step(k)
-        out.append(_snap(ft))
+        out.append(snap(ft))
         ft.close()
     assert (out[0]["steps"] == 7).any()
-    _assert_same(out[0], out[1], "3 + 4 steps against 7")
+    assert_same(out[0], out[1], "3 + 4 steps against 7", LOOP_BUFFERS_MASK)
 
 
 def test_longest_first_dispatch_order(cuda, golden):
@@ -264,15 +215,14 @@ def test_longest_first_dispatch_order(cuda, golden):
     import torch
     from mpcqp.control.ref_builder import build_reference
     from mpcqp.pipeline.fleet import initial_states
-    from test_gpu_fleet import _varied_fleet
 
     N, steps = 3, 4
     V = 8 * torch.cuda.get_device_properties(0).multi_processor_count + 5
-    _, paths, starts, goals = _varied_fleet(golden, V, seed=6)
+    _, paths, starts, goals = varied_fleet(golden, V, seed=6)
     names = ["default", "dt_0.2", "wheelbase_14px"]
-    blocks = [_block(name, N) for name in names]
+    blocks = variant_blocks(N, names)
     cls = np.arange(V) % 3
-    distinct = {}  # _varied_fleet cycles through 13 plans: one reference per (plan, dt)
+    distinct = {}  # varied_fleet cycles through 13 plans: one reference per (plan, dt)
 
     def ref_of(v):
         key = (v % 13, blocks[cls[v]].dt)
@@ -284,21 +234,21 @@ def test_longest_first_dispatch_order(cuda, golden):
         assert paths[v] is paths[v - 13]
     refs = [ref_of(v) for v in range(V)]
     s0 = initial_states(paths, starts)
-    ft = _tracker(N, V, steps)
+    ft = fleet_tracker(N, V, M_REF, steps, fused=True)
     ft.set_classes(blocks)
     ft.reset(refs, s0, goals, classes=cls)
     ft.run()
-    got = _snap(ft)
+    got = snap(ft)
     ft.close()
     assert (got["steps"] == steps).any()
     for c, block in enumerate(blocks):
         idx = np.flatnonzero(cls == c)
-        h = _tracker(N, len(idx), steps, params=block)
+        h = fleet_tracker(N, len(idx), M_REF, steps, fused=True, params=block)
         h.reset(_sub(refs, idx), s0[idx], goals[idx])
         h.run()
-        want = _snap(h)
+        want = snap(h)
         h.close()
-        _assert_same(_rows(got, idx), want, f"class {c}")
+        assert_same(_rows(got, idx), want, f"class {c}", LOOP_BUFFERS_MASK)
 
 
 def _raw_mixed(ft, steps=2):
@@ -316,20 +266,19 @@ def test_mixed_loop_refusals(cuda, golden):
     import torch
     from mpcqp import _lib
     from mpcqp.pipeline.fleet import relaxed_parameters
-    from test_gpu_fleet import _varied_fleet
 
     V, max_steps = 4, 12
-    _, paths, starts, goals = _varied_fleet(golden, V, seed=8)
+    _, paths, starts, goals = varied_fleet(golden, V, seed=8)
 
     def fresh(N, **settings):
-        ft = _tracker(N, V, max_steps, **settings)
+        ft = fleet_tracker(N, V, M_REF, max_steps, fused=True, **settings)
         ft.reset_from_plans(paths, starts, goals)
         return ft
 
     # a class table on one workspace only, and tables of different sizes
     ft = fresh(10)
     p = ft.params
-    before = _snap(ft)
+    before = snap(ft)
     ft._nominal.set_classes([p, p])
     rc, msg = _raw_mixed(ft)
     assert rc == E_STATE and "relaxed workspace" in msg, (rc, msg)
@@ -339,7 +288,7 @@ def test_mixed_loop_refusals(cuda, golden):
     ft._nominal.set_classes(None)
     rc, msg = _raw_mixed(ft)
     assert rc == E_STATE and "nominal workspace" in msg, (rc, msg)
-    _assert_same(_snap(ft), before, "after the refused calls")
+    assert_same(snap(ft), before, "after the refused calls", LOOP_BUFFERS_MASK)
     ft.close()
 
     # parameter blocks that do not run the fused kernel: refused, nothing enqueued
@@ -347,10 +296,10 @@ def test_mixed_loop_refusals(cuda, golden):
         ft = fresh(N, **settings)
         ft._nominal.set_classes([ft.params])
         ft._relaxed.set_classes([relaxed_parameters(ft.params)])
-        before = _snap(ft)
+        before = snap(ft)
         rc, msg = _raw_mixed(ft)
         assert rc == E_HORIZON and "fused" in msg, (N, settings, rc, msg)
-        _assert_same(_snap(ft), before, f"N = {N} {settings}: fleet buffers after the refusal")
+        assert_same(snap(ft), before, f"N = {N} {settings}: fleet buffers after the refusal", LOOP_BUFFERS_MASK)
         if N > 32:  # the tracker itself refuses earlier
             with pytest.raises(ValueError, match="horizon <= 32"):
                 ft.set_classes([ft.params])
@@ -363,7 +312,7 @@ def test_mixed_loop_refusals(cuda, golden):
     x0 = np.tile([10.0, 10.0, 0.0, 5.0], (V, 1))
     ref = np.tile(np.array([[10.0 + 1.5 * k, 10.0, 0.0, 15.0] for k in range(N + 1)]), (V, 1, 1))
     ctrl.solve_batch(x0, ref)
-    ft.set_classes([ft.params, _block("dt_0.2", N)])
+    ft.set_classes([ft.params, variant_params("dt_0.2", N)])
     ft.reset_from_plans(paths, starts, goals, classes=np.array([0, 1, 1, 0]))
     ft.step(3)
     torch.cuda.synchronize()
@@ -375,6 +324,7 @@ def test_mixed_loop_refusals(cuda, golden):
     ft.reset_from_plans(paths, starts, goals)
     s = ctypes.c_void_p(torch.cuda.current_stream(ft.device).cuda_stream)
     assert L.mpcqp_fleet_loop(ft._nominal._ws, ft._relaxed._ws, ctypes.byref(ft._fleet), max_steps, s) == 0
-    got = _snap(ft)
+    got = snap(ft)
     ft.close()
-    _assert_same(got, _homogeneous(N, max_steps, None, paths, starts, goals), "plain loop after a mixed one")
+    assert_same(got, _homogeneous(N, max_steps, None, paths, starts, goals), "plain loop after a mixed one",
+                LOOP_BUFFERS_MASK)

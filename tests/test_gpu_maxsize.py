@@ -12,6 +12,7 @@ oracle by the parity tests (test_gpu_parity.py, test_gpu_wide.py).
 from __future__ import annotations
 
 import pytest
+from gpu_helpers import base_params
 
 pytestmark = pytest.mark.gpu
 
@@ -19,11 +20,10 @@ pytestmark = pytest.mark.gpu
 def _tiled_equal(cuda, horizon: int, base_batch: int, copies: int, min_bytes: int) -> None:
     import torch
     from mpcqp import scenarios
-    from mpcqp.config import MPCConfig
     from mpcqp.control.mpc_controller import BatchedMPCController
 
     b = scenarios.config3(base_batch, horizon=horizon, seed=9100 + horizon)
-    params = MPCConfig(horizon=horizon).to_parameters(0.8)
+    params = base_params(horizon)
     x0 = torch.as_tensor(b.x0, device=cuda)
     ref = torch.as_tensor(b.ref, device=cuda)
     up = torch.as_tensor(b.u_prev, device=cuda)
@@ -61,7 +61,7 @@ def test_workspace_buffers_allocated_at_first_use(cuda):
 
     L = _lib.lib()
     b = scenarios.config3(64)
-    params = MPCConfig(horizon=20).to_parameters(0.8)
+    params = base_params(20)
     ctrl = BatchedMPCController(params, 64, device=cuda)
     ctrl.solve_batch(b.x0, b.ref, b.u_prev)
     assert not L.mpcqp_model_buffer(ctrl._ws) and not L.mpcqp_state_buffer(ctrl._ws)
@@ -72,7 +72,7 @@ def test_workspace_buffers_allocated_at_first_use(cuda):
     assert L.mpcqp_model_buffer(dbg._ws) and L.mpcqp_state_buffer(dbg._ws)
     assert int((s.status == 1).sum()) == 64
     dbg.close()
-    wide = BatchedMPCController(MPCConfig(horizon=40).to_parameters(0.8), 8, device=cuda)
+    wide = BatchedMPCController(base_params(40), 8, device=cuda)
     assert L.mpcqp_model_buffer(wide._ws) and L.mpcqp_state_buffer(wide._ws)
     wide.close()
 

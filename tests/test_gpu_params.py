@@ -17,40 +17,10 @@ from __future__ import annotations
 
 import numpy as np
 import pytest
+from gpu_helpers import FAIL_NOMINAL, REL_TOL, assert_exact, base_params, rel, solve, variant_params
 from param_variants import VARIANTS
 
 pytestmark = pytest.mark.gpu
-
-REL_TOL = 1e-8
-FAIL_NOMINAL = dict(max_iter=1, polish=0, polish_from=0, polish_near=0.0)
-
-
-def _base(N, res=0.8):
-    from mpcqp.config import MPCConfig
-
-    return MPCConfig(horizon=N).to_parameters(res)
-
-
-def _variant(name, N):
-    from param_variants import resolution, variant
-
-    return variant(_base(N, resolution(name)), name)
-
-
-def _solve(params, x0, ref, u_prev, **settings):
-    import torch
-    from mpcqp.control.mpc_controller import BatchedMPCController
-
-    ctrl = BatchedMPCController(params, len(x0), device="cuda:0", **settings)
-    sol = ctrl.solve_batch(x0, ref, u_prev)
-    torch.cuda.synchronize()
-    out = {k: getattr(sol, k).cpu().numpy().copy() for k in sol._fields}
-    ctrl.close()
-    return out
-
-
-def _rel(a, b):
-    return float(np.abs(a - b).max() / max(1.0, np.abs(b).max()))
 
 
 @pytest.mark.parametrize("N", [10, 20, 30])
@@ -59,17 +29,15 @@ def test_parameter_block_matches_exact_oracle(cuda, name, N):
     import mpc_oracle as mo
     from mpcqp import scenarios
 
-    params = _variant(name, N)
+    params = variant_params(name, N)
     batch = scenarios.config3(48, horizon=N, seed=1000 + N)
-    out = _solve(params, batch.x0, batch.ref, batch.u_prev)
+    out = solve(params, batch.x0, batch.ref, batch.u_prev)
     assert (out["status"] == 1).all(), np.unique(out["status"], return_counts=True)
     n_active = 0
     for b in range(batch.size):
         ex = mo.solve_exact(params, batch.x0[b], batch.ref[b], batch.u_prev[b])
         assert ex.converged
-        e = max(_rel(out["U"][b], ex.Umat), _rel(out["X"][b], ex.X), _rel(out["u0"][b], ex.Umat[:, 0]))
-        assert e <= REL_TOL, f"{name} N={N} QP {b}: rel err {e:.3e}"
-        assert np.array_equal(out["active"][b], ex.active), f"{name} N={N} QP {b}: active set differs"
+        assert_exact(out, b, ex, f"{name} N={N}")
         n_active += int((ex.active != 0).any())
     assert n_active > 0  # the variant's soft rows are exercised
 
@@ -81,12 +49,12 @@ def test_parameter_block_matches_c_restatement(cuda):
 
     batch = scenarios.config3(128, horizon=20, seed=77)
     for name in VARIANTS:
-        params = _variant(name, 20)
-        out = _solve(params, batch.x0, batch.ref, batch.u_prev)
+        params = variant_params(name, 20)
+        out = solve(params, batch.x0, batch.ref, batch.u_prev)
         ref = cpu_solver.cpu_solve(params, batch.x0, batch.ref, batch.u_prev)
         assert np.array_equal(out["status"], ref["status"]), name
         assert np.array_equal(out["active"], ref["active"]), name
-        assert _rel(out["U"], ref["U"]) <= REL_TOL, name
+        assert rel(out["U"], ref["U"]) <= REL_TOL, name
 
 
 def test_max_iter_status_follows_osqp(cuda):
@@ -96,11 +64,11 @@ def test_max_iter_status_follows_osqp(cuda):
     from mpcqp import scenarios
 
     batch = scenarios.config3(256, horizon=20, seed=5)
-    params = _base(20)
+    params = base_params(20)
     seen = set()
     for max_iter in (1, 30, 60, 100):
         st = dict(max_iter=max_iter, polish_from=0, polish_near=0.0)
-        out = _solve(params, batch.x0, batch.ref, batch.u_prev, **st)
+        out = solve(params, batch.x0, batch.ref, batch.u_prev, **st)
         ref = cpu_solver.cpu_solve(params, batch.x0, batch.ref, batch.u_prev, **st)
         agree = (out["status"] == ref["status"]).mean()
         assert agree >= 0.99, (max_iter, agree)
@@ -126,7 +94,7 @@ def test_relaxed_retry_succeeds_host(cuda):
     from mpcqp.pipeline.fleet import relaxed_parameters
 
     x0, window, up = _window_case()
-    params = MPCConfig(horizon=15).to_parameters(0.8)
+    params = base_params(15)
     assert MPCController(params, **FAIL_NOMINAL).solve(x0, window, u_prev=up) == (None, None, None)
     tr = TrajectoryTracker(MPCConfig(horizon=15), VizConfig(), solver_settings=FAIL_NOMINAL)
     u0, X, U = tr._solve_with_relaxation(x0, window, up, params)
@@ -134,10 +102,10 @@ def test_relaxed_retry_succeeds_host(cuda):
     w6 = np.array(window, copy=True)
     w6[:, 3] *= 0.6
     ex = mo.solve_exact(relaxed_parameters(params), x0, w6, up)
-    assert _rel(U, ex.Umat) <= REL_TOL and _rel(X, ex.X) <= REL_TOL
+    assert rel(U, ex.Umat) <= REL_TOL and rel(X, ex.X) <= REL_TOL
     # and the relaxed optimum differs from the nominal one (the retry changed the answer)
     nom = mo.solve_exact(params, x0, window, up)
-    assert _rel(U, nom.Umat) > 1e-3
+    assert rel(U, nom.Umat) > 1e-3
 
 
 @pytest.mark.parametrize("fused", [False, True])
@@ -168,7 +136,7 @@ def test_relaxed_retry_succeeds_fleet(cuda, fused):
         w[:, 3] *= 0.6
         s0 = initial_state(paths[v], starts[v])
         ex = mo.solve_exact(rp, s0, w, np.zeros(2))
-        assert _rel(res.inputs[v][0], ex.Umat[:, 0]) <= REL_TOL
+        assert rel(res.inputs[v][0], ex.Umat[:, 0]) <= REL_TOL
         nxt = mo.f_discrete(s0, res.inputs[v][0], params.dt, params.wheelbase_px)
         np.testing.assert_allclose(res.states[v][0], nxt, rtol=0, atol=1e-9)
     ft.close()

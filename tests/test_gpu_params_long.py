@@ -37,42 +37,27 @@ from functools import lru_cache
 
 import numpy as np
 import pytest
-from param_variants import VARIANTS, resolution, variant
+from gpu_helpers import REL_TOL, assert_exact, controller, rel, solve, solve_with_model, variant_params
+from param_variants import VARIANTS
 
 pytestmark = pytest.mark.gpu
 
-REL_TOL = 1e-8  # the project's tolerance against the exact oracle (test_gpu_params.py)
 MID_N = (33, 40, 49, 64)
 FAST_N = MID_N + (65, 72)
 EDGE_N = (33, 40, 49, 64, 65)
 EDGE_BLOCKS = ("default", "tight_bounds", "q_nondiag")
 
 
-def _block(name, N):
-    from mpcqp.config import MPCConfig
-
-    if name == "default":
-        return MPCConfig(horizon=N).to_parameters(0.8)
-    return variant(MPCConfig(horizon=N).to_parameters(resolution(name)), name)
-
-
-def _rel(a, b):
-    return float(np.abs(a - b).max() / max(1.0, np.abs(b).max()))
-
-
-def _assert_matches_exact_oracle(params, x0, ref, u_prev, out, what):
-    """Every QP of ``out`` against solve_exact under ``params``; returns the oracle's active sets (B, 5N+1)."""
+def _exact_active_sets(params, x0, ref, u_prev, out, what):
+    """Every QP of ``out`` solved and equal to solve_exact under ``params`` (gpu_helpers.assert_exact); returns
+    the oracle's active sets (B, 5N+1)."""
     import mpc_oracle as mo
 
-    assert (out["status"] == 1).all(), (what, np.unique(out["status"], return_counts=True))
     acts = []
     for b in range(len(x0)):
         ex = mo.solve_exact(params, x0[b], ref[b], None if u_prev is None else u_prev[b])
         assert ex.converged, f"{what} QP {b}: the oracle did not converge"
-        e = max(_rel(out["U"][b], ex.Umat), _rel(out["X"][b], ex.X), _rel(out["u0"][b], ex.Umat[:, 0]))
-        assert e <= REL_TOL, f"{what} QP {b}: rel err {e:.3e}"
-        assert np.array_equal(out["active"][b], ex.active), \
-            f"{what} QP {b}: active set differs in rows {np.flatnonzero(out['active'][b] != ex.active)[:10]}"
+        assert_exact(out, b, ex, what, solved=True)
         acts.append(ex.active)
     return np.stack(acts)
 
@@ -81,11 +66,10 @@ def _assert_matches_exact_oracle(params, x0, ref, u_prev, out, what):
 def _fast_case(name, N):
     """The 12-QP batch of part 1 under variant ``name``, solved once in fast mode: (params, batch, out, model)."""
     from mpcqp import scenarios
-    from test_gpu_wide import _solve_with_model
 
-    params = _block(name, N)
+    params = variant_params(name, N)
     batch = scenarios.config3(12, horizon=N, seed=6000 + N)
-    out, model = _solve_with_model(params, batch.x0, batch.ref, batch.u_prev)
+    out, model = solve_with_model(params, batch.x0, batch.ref, batch.u_prev)
     assert model is not None  # the mid and wide kernels read the model K1 wrote
     for a in (*out.values(), model):
         a.setflags(write=False)  # shared by parts 1 and 3
@@ -97,7 +81,7 @@ def _fast_case(name, N):
 @pytest.mark.parametrize("name", VARIANTS)
 def test_variants_match_exact_oracle_on_mid_and_wide(cuda, name, N):
     params, batch, out, _ = _fast_case(name, N)
-    acts = _assert_matches_exact_oracle(params, batch.x0, batch.ref, batch.u_prev, out, f"{name} N={N}")
+    acts = _exact_active_sets(params, batch.x0, batch.ref, batch.u_prev, out, f"{name} N={N}")
     assert (acts != 0).any()  # the variant's soft rows are exercised
 
 
@@ -108,11 +92,10 @@ def test_variants_reproducible_mode_bit_exact_with_c_restatement(cuda, name, N):
     """The mode's guarantee (same model in -> same bits out as oracle/mpcqp_cpu.c) under every variant."""
     import cpu_solver
     from mpcqp import scenarios
-    from test_gpu_wide import _solve_with_model
 
-    params = _block(name, N)
+    params = variant_params(name, N)
     batch = scenarios.config3(12, horizon=N, seed=6100 + N)
-    out, model = _solve_with_model(params, batch.x0, batch.ref, batch.u_prev, reproducible=1)
+    out, model = solve_with_model(params, batch.x0, batch.ref, batch.u_prev, reproducible=1)
     assert model is not None
     ref = cpu_solver.cpu_solve_models(params, model)
     assert np.array_equal(out["status"], ref["status"])
@@ -165,10 +148,10 @@ def test_variants_mid_kernel_against_c_restatement(cuda, name, N):
     same = int((out["iters"] == ref["iters"]).all(axis=1).sum())
     _AGREEMENT[name, N] = same
     print(f"{name} N={N}: {same} of {len(model)} QPs agree on all four counters; "
-          f"rel U {_rel(out['U'], ref['U']):.3e}")
+          f"rel U {rel(out['U'], ref['U']):.3e}")
     assert np.array_equal(out["status"], ref["status"])
     assert np.array_equal(out["active"], ref["active"])
-    assert _rel(out["U"], ref["U"]) <= REL_TOL
+    assert rel(out["U"], ref["U"]) <= REL_TOL
 
 
 # ---------------------------------------------------------------------- 4. edge inputs
@@ -226,15 +209,13 @@ def _assert_edge_coverage(act, N, what):
 @pytest.mark.parametrize("N", EDGE_N)
 @pytest.mark.parametrize("name", EDGE_BLOCKS)
 def test_edge_inputs_on_mid_and_wide(cuda, name, N, with_u_prev):
-    from test_gpu_params import _solve
-
-    params = _block(name, N)
+    params = variant_params(name, N)
     x0, ref, up = _edge_batch(N)
     if not with_u_prev:
         up = None
-    out = _solve(params, x0, ref, up)
+    out = solve(params, x0, ref, up)
     what = f"{name} N={N} {'with' if with_u_prev else 'without'} u_prev"
-    acts = _assert_matches_exact_oracle(params, x0, ref, up, out, what)
+    acts = _exact_active_sets(params, x0, ref, up, out, what)
     _assert_edge_coverage(acts, N, what)
 
 
@@ -245,12 +226,11 @@ def test_null_outputs_on_mid_and_wide(cuda, N):
     Buffers not passed are not passed at all (no undersized or poisoned stand-ins)."""
     import torch
     from mpcqp import _lib, scenarios
-    from mpcqp.control.mpc_controller import BatchedMPCController
 
     B = 8
-    params = _block("default", N)
+    params = variant_params("default", N)
     batch = scenarios.config3(B, horizon=N, seed=8000 + N)
-    ctrl = BatchedMPCController(params, B, device="cuda:0")
+    ctrl = controller(params, B)
     L = _lib.lib()
     x0, ref, up = (torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0") for a in (batch.x0, batch.ref, batch.u_prev))
     dev = dict(device="cuda:0")

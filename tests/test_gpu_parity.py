@@ -10,47 +10,9 @@ from __future__ import annotations
 
 import numpy as np
 import pytest
+from gpu_helpers import OUTS, REL_TOL, base_params, check_against_oracle, controller, d2h, rel, solve, take
 
 pytestmark = pytest.mark.gpu
-
-REL_TOL = 1e-8
-
-
-def _params(N, map_resolution=0.8):
-    from mpcqp.config import MPCConfig
-
-    return MPCConfig(horizon=N).to_parameters(map_resolution)
-
-
-def _solve(params, x0, ref, u_prev, method="admm", **settings):
-    import torch
-    from mpcqp.control.mpc_controller import BatchedMPCController
-
-    ctrl = BatchedMPCController(params, max(1, len(x0)), device="cuda:0", method=method, **settings)
-    sol = ctrl.solve_batch(x0, ref, u_prev)
-    torch.cuda.synchronize()
-    out = {k: getattr(sol, k).cpu().numpy().copy() for k in sol._fields}
-    ctrl.close()
-    return out
-
-
-def _rel(a, b):
-    return float(np.abs(a - b).max() / max(1.0, np.abs(b).max()))
-
-
-def _check_against_oracle(params, x0, ref, u_prev, out, idx):
-    import mpc_oracle as mo
-
-    worst = 0.0
-    for b in idx:
-        ex = mo.solve_exact(params, x0[b], ref[b], None if u_prev is None else u_prev[b])
-        assert ex.converged
-        e = max(_rel(out["U"][b], ex.Umat), _rel(out["X"][b], ex.X), _rel(out["u0"][b], ex.Umat[:, 0]))
-        worst = max(worst, e)
-        assert e <= REL_TOL, f"QP {b}: rel err {e:.3e}"
-        assert np.array_equal(out["active"][b], ex.active), f"QP {b}: active set differs"
-    return worst
-
 
 @pytest.mark.parametrize("cfg", ["config2", "config3", "config4"])
 def test_batches_match_exact_oracle(cuda, cfg):
@@ -58,21 +20,21 @@ def test_batches_match_exact_oracle(cuda, cfg):
 
     batch = {"config2": lambda: scenarios.config2(1024), "config3": lambda: scenarios.config3(512),
              "config4": lambda: scenarios.config4(512)}[cfg]()
-    params = _params(batch.horizon)
-    out = _solve(params, batch.x0, batch.ref, batch.u_prev)
+    params = base_params(batch.horizon)
+    out = solve(params, batch.x0, batch.ref, batch.u_prev)
     assert (out["status"] == 1).all(), np.unique(out["status"], return_counts=True)
-    _check_against_oracle(params, batch.x0, batch.ref, batch.u_prev, out, range(0, batch.size, 7))
+    check_against_oracle(params, batch.x0, batch.ref, batch.u_prev, out, range(0, batch.size, 7))
 
 
 def test_newton_method_matches(cuda):
     from mpcqp import scenarios
 
     batch = scenarios.config3(256)
-    params = _params(20)
-    out = _solve(params, batch.x0, batch.ref, batch.u_prev, method="newton")
+    params = base_params(20)
+    out = solve(params, batch.x0, batch.ref, batch.u_prev, method="newton")
     assert (out["status"] == 1).all()
     assert (out["iters"][:, 0] == 0).all()
-    _check_against_oracle(params, batch.x0, batch.ref, batch.u_prev, out, range(0, 256, 5))
+    check_against_oracle(params, batch.x0, batch.ref, batch.u_prev, out, range(0, 256, 5))
 
 
 @pytest.mark.parametrize("cfg,N,B", [("config2", 20, 1024), ("config3", 4, 1024), ("config3", 8, 1024),
@@ -90,14 +52,14 @@ def test_iteration_indexing_bit_exact_on_product_path(cuda, cfg, N, B):
     batch = {"config2": lambda: scenarios.config2(B),
              "config3": lambda: scenarios.config3(B, horizon=N, seed=5000 + N),
              "config4": lambda: scenarios.config4(B)}[cfg]()
-    params = _params(batch.horizon)
-    out = _solve(params, batch.x0, batch.ref, batch.u_prev)
+    params = base_params(batch.horizon)
+    out = solve(params, batch.x0, batch.ref, batch.u_prev)
     ref = cpu_solver.cpu_solve(params, batch.x0, batch.ref, batch.u_prev)
     same = (out["iters"] == ref["iters"]).all(axis=1)
     assert same.all(), f"QPs {np.flatnonzero(~same)[:10]} disagree on iteration counts"
     assert np.array_equal(out["status"], ref["status"])
     assert np.array_equal(out["active"], ref["active"])
-    assert _rel(out["U"], ref["U"]) <= REL_TOL
+    assert rel(out["U"], ref["U"]) <= REL_TOL
 
 
 @pytest.mark.parametrize("schedule", [
@@ -115,8 +77,8 @@ def test_iteration_counts_match_cpu_restatement(cuda, schedule):
     from mpcqp import scenarios
 
     batch = scenarios.config3(512)
-    params = _params(20)
-    out = _solve(params, batch.x0, batch.ref, batch.u_prev, **schedule)
+    params = base_params(20)
+    out = solve(params, batch.x0, batch.ref, batch.u_prev, **schedule)
     ref = cpu_solver.cpu_solve(params, batch.x0, batch.ref, batch.u_prev, **schedule)
     assert (out["status"] == 1).all()
     same = (out["iters"] == ref["iters"]).all(axis=1)
@@ -126,56 +88,44 @@ def test_iteration_counts_match_cpu_restatement(cuda, schedule):
     assert same.all(), f"QPs {np.flatnonzero(~same)[:10]} disagree on iteration counts"
     assert np.array_equal(out["status"], ref["status"])
     assert np.array_equal(out["active"], ref["active"])
-    assert _rel(out["U"], ref["U"]) <= REL_TOL
+    assert rel(out["U"], ref["U"]) <= REL_TOL
 
 
 def test_k1_model_matches_restatement(cuda):
     """K1 (unwrap + linearize) against the C restatement and numpy's unwrap."""
-    import ctypes
-
     import cpu_solver
     import torch
     from mpcqp import _lib, scenarios
-    from mpcqp.control.mpc_controller import BatchedMPCController
 
     batch = scenarios.config3(256)
     # inject 2pi yaw jumps so np.unwrap has work to do
     ref = batch.ref.copy()
     ref[::3, 7:, 2] += 2 * np.pi
     ref[1::3, 12:, 2] -= 4 * np.pi
-    params = _params(20)
+    params = base_params(20)
     # debug_state: K1 runs as its own kernel and leaves the model in the workspace (otherwise it
     # is fused into the solve and never leaves the CU)
-    ctrl = BatchedMPCController(params, 256, device="cuda:0", debug_state=1)
+    ctrl = controller(params, 256, debug_state=1)
     ctrl.solve_batch(batch.x0, ref, batch.u_prev)
     torch.cuda.synchronize()
     S = _lib.lib().mpcqp_model_stride(20)
-    ptr = _lib.lib().mpcqp_model_buffer(ctrl._ws)
-    host = np.zeros((256, S))
-    hip = ctypes.CDLL("libamdhip64.so")
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    assert hip.hipMemcpy(host.ctypes.data, ptr, host.nbytes, 2) == 0  # device -> host
+    host = d2h(_lib.lib().mpcqp_model_buffer(ctrl._ws), np.zeros((256, S)))
     cpu = cpu_solver.cpu_solve(params, batch.x0, ref, batch.u_prev, want_model=True)["model"]
     N = 20
     yaw_gpu = host[:, 7 * N + 2: 11 * N + 4: 4]
     yaw_np = np.unwrap(ref[:, :, 2], axis=1)
     assert np.array_equal(yaw_gpu, yaw_np)
-    assert _rel(host[:, : 11 * N + 10], cpu[:, : 11 * N + 10]) <= 1e-12
+    assert rel(host[:, : 11 * N + 10], cpu[:, : 11 * N + 10]) <= 1e-12
     ctrl.close()
 
 
 def test_k1_unwrap_golden_exact_pi(cuda, golden):
     """The reference-generated np.unwrap fixtures (unwrap.npz: exact +-pi jumps, whose sign rule
     is numpy's `ddmod == -pi and dd > 0`) through K1 on the GPU, bit for bit."""
-    import ctypes
-
     import torch
     from mpcqp import _lib
-    from mpcqp.control.mpc_controller import BatchedMPCController
 
     g = golden("unwrap.npz")
-    hip = ctypes.CDLL("libamdhip64.so")
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
     for case in range(len(g["lens"])):
         n = int(g["lens"][case])
         N = n - 1
@@ -183,12 +133,11 @@ def test_k1_unwrap_golden_exact_pi(cuda, golden):
         ref[:, :, 0] = np.arange(n)
         ref[:, :, 2] = g["p"][case, :n]
         ref[:, :, 3] = 10.0
-        ctrl = BatchedMPCController(_params(N), 2, device="cuda:0", debug_state=1)
+        ctrl = controller(base_params(N), 2, debug_state=1)
         ctrl.solve_batch(np.zeros((2, 4)), ref, np.zeros((2, 2)))
         torch.cuda.synchronize()
         S = _lib.lib().mpcqp_model_stride(N)
-        host = np.zeros((2, S))
-        assert hip.hipMemcpy(host.ctypes.data, _lib.lib().mpcqp_model_buffer(ctrl._ws), host.nbytes, 2) == 0
+        host = d2h(_lib.lib().mpcqp_model_buffer(ctrl._ws), np.zeros((2, S)))
         yaw = host[:, 7 * N + 2: 11 * N + 4: 4]
         assert np.array_equal(yaw[0], g["unwrapped"][case, :n]), case
         assert np.array_equal(yaw[1], g["unwrapped"][case, :n]), case
@@ -201,10 +150,10 @@ def test_fused_k1_equals_separate_k1(cuda):
     from mpcqp import scenarios
 
     batch = scenarios.config3(256)
-    params = _params(20)
-    a = _solve(params, batch.x0, batch.ref, batch.u_prev)
-    b = _solve(params, batch.x0, batch.ref, batch.u_prev, debug_state=1)
-    for k in ("u0", "X", "U", "status", "iters", "active"):
+    params = base_params(20)
+    a = solve(params, batch.x0, batch.ref, batch.u_prev)
+    b = solve(params, batch.x0, batch.ref, batch.u_prev, debug_state=1)
+    for k in OUTS:
         assert np.array_equal(a[k], b[k]), k
 
 
@@ -214,24 +163,20 @@ def test_debug_scalars_of_the_solve_driver(cuda, N):
     5 / 6 = the polish's factorizations from scratch / rank-1 updates, 7 = its start time.  A polish
     pass always begins with a factorization from scratch, and the debug state changes no output bit.
     For one-wave horizons only: from MPCQP_WIDE_MIN_HORIZON on the state slice has the wide layout."""
-    import torch
     from mpcqp import _lib, scenarios
-    from mpcqp.control.mpc_controller import BatchedMPCController
 
     B = 8
     batch = scenarios.config3(B, horizon=N)
-    params = _params(N)
-    plain = _solve(params, batch.x0, batch.ref, batch.u_prev)
-    ctrl = BatchedMPCController(params, B, device="cuda:0", debug_state=1)
-    sol = ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev)
-    torch.cuda.synchronize()
-    out = {k: getattr(sol, k).cpu().numpy().copy() for k in sol._fields}
+    params = base_params(N)
+    plain = solve(params, batch.x0, batch.ref, batch.u_prev)
+    ctrl = controller(params, B, debug_state=1)
+    out = take(ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev))
     L = _lib.lib()
     SS = L.mpcqp_state_stride(N)
     sc = SS - 8  # the eight scalars close a QP's slice
     if N == 20:
         assert sc == (4 * 20 * 20 + 7) // 8 * 8 + 15 * 64  # where tools/qp_cycles.py reads them
-    st = _d2h(L.mpcqp_state_buffer(ctrl._ws), np.zeros((B, SS)))
+    st = d2h(L.mpcqp_state_buffer(ctrl._ws), np.zeros((B, SS)))
     ctrl.close()
     cycles, n_full, n_r1, start = (st[:, sc + k] for k in (4, 5, 6, 7))
     print(f"N={N}: cycles {cycles}, n_full {n_full}, n_r1 {n_r1}, start {start}, iters {out['iters'].tolist()}")
@@ -241,7 +186,7 @@ def test_debug_scalars_of_the_solve_driver(cuda, N):
         assert np.array_equal(v, np.round(v)) and (v >= 0).all()
     polished = out["iters"][:, 1] >= 1
     assert (n_full[polished] >= 1).all()
-    for k in ("u0", "X", "U", "status", "iters", "active"):
+    for k in OUTS:
         assert np.array_equal(plain[k], out[k]), k
 
 
@@ -258,10 +203,10 @@ def test_horizons(cuda, N):
     ref = np.stack([scenarios.window(ref_g, int(o), N) for o in offs])
     x0 = ref[:, 0] + rng.normal(0, 1, (B, 4)) * [2, 2, 0.3, 2]
     u_prev = rng.normal(0, 1, (B, 2)) * [3, 0.05]
-    params = _params(N)
-    out = _solve(params, x0, ref, u_prev)
+    params = base_params(N)
+    out = solve(params, x0, ref, u_prev)
     assert (out["status"] == 1).all()
-    _check_against_oracle(params, x0, ref, u_prev, out, range(0, B, 3))
+    check_against_oracle(params, x0, ref, u_prev, out, range(0, B, 3))
 
 
 def test_edge_cases(cuda):
@@ -271,7 +216,7 @@ def test_edge_cases(cuda):
     from mpcqp import scenarios
 
     N = 15
-    params = _params(N)
+    params = base_params(N)
     batch = scenarios.config3(16, horizon=N)
     x0 = batch.x0.copy()
     ref = batch.ref.copy()
@@ -282,14 +227,14 @@ def test_edge_cases(cuda):
     ref[3, 5:, 2] -= 2 * np.pi  # wraps through pi
     up = batch.u_prev.copy()
     up[4] = [60.0, 1.0]   # outside the input box and the rate band
-    out = _solve(params, x0, ref, up)
+    out = solve(params, x0, ref, up)
     assert (out["status"] == 1).all()
-    _check_against_oracle(params, x0, ref, up, out, range(16))
+    check_against_oracle(params, x0, ref, up, out, range(16))
     assert out["active"][0, 0] == 1 and out["active"][1, 0] == 2  # constant v0 row
-    out2 = _solve(params, x0, ref, None)
+    out2 = solve(params, x0, ref, None)
     assert (out2["status"] == 1).all()
     ex = mo.solve_exact(params, x0[5], ref[5], None)
-    assert _rel(out2["U"][5], ex.Umat) <= REL_TOL
+    assert rel(out2["U"][5], ex.Umat) <= REL_TOL
 
 
 def test_empty_batch_and_errors(cuda):
@@ -297,10 +242,9 @@ def test_empty_batch_and_errors(cuda):
 
     import torch
     from mpcqp import _lib
-    from mpcqp.control.mpc_controller import BatchedMPCController
 
-    params = _params(10)
-    ctrl = BatchedMPCController(params, 4, device="cuda:0")
+    params = base_params(10)
+    ctrl = controller(params, 4)
     L = _lib.lib()
     st = torch.zeros(4, dtype=torch.int32, device="cuda:0")
     x0 = torch.zeros((4, 4), dtype=torch.float64, device="cuda:0")
@@ -330,13 +274,13 @@ def test_full_size_config3_properties(cuda):
     from mpcqp import scenarios
 
     batch = scenarios.config3(4096)
-    params = _params(20)
-    a = _solve(params, batch.x0, batch.ref, batch.u_prev)
-    b = _solve(params, batch.x0, batch.ref, batch.u_prev)
+    params = base_params(20)
+    a = solve(params, batch.x0, batch.ref, batch.u_prev)
+    b = solve(params, batch.x0, batch.ref, batch.u_prev)
     assert (a["status"] == 1).all()
     for k in ("U", "X", "active", "iters"):
         assert np.array_equal(a[k], b[k]), f"non-deterministic {k}"
-    _check_against_oracle(params, batch.x0, batch.ref, batch.u_prev, a, range(0, 4096, 97))
+    check_against_oracle(params, batch.x0, batch.ref, batch.u_prev, a, range(0, 4096, 97))
 
 
 def test_full_size_config4_properties(cuda):
@@ -346,8 +290,8 @@ def test_full_size_config4_properties(cuda):
     from mpcqp import scenarios
 
     batch = scenarios.config4(16384)
-    params = _params(30)
-    out = _solve(params, batch.x0, batch.ref, batch.u_prev)
+    params = base_params(30)
+    out = solve(params, batch.x0, batch.ref, batch.u_prev)
     assert (out["status"] == 1).all()
     for b in range(0, 16384, 331):
         qp = mo.condense(params, batch.x0[b], batch.ref[b], batch.u_prev[b])
@@ -358,16 +302,6 @@ def test_full_size_config4_properties(cuda):
         lo, hi = params.v_bounds
         codes = np.where(v > hi, 2, np.where(v < lo, 1, 0))
         assert np.array_equal(codes, out["active"][b, :31])
-
-
-def _d2h(ptr, nbytes_array):
-    import ctypes
-
-    hip = ctypes.CDLL("libamdhip64.so")
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    hip.hipDeviceSynchronize()
-    assert hip.hipMemcpy(nbytes_array.ctypes.data, ptr, nbytes_array.nbytes, 2) == 0
-    return nbytes_array
 
 
 def test_wave_primitives(cuda):
@@ -401,30 +335,29 @@ def test_setup_state_matches_restatement(cuda, N):
     import cpu_solver
     import torch
     from mpcqp import _lib, scenarios
-    from mpcqp.control.mpc_controller import BatchedMPCController
 
     batch = scenarios.config3(64, horizon=N)
-    params = _params(N)
-    ctrl = BatchedMPCController(params, 64, device="cuda:0", debug_state=1)  # write the state buffer
+    params = base_params(N)
+    ctrl = controller(params, 64, debug_state=1)  # write the state buffer
     ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev)
     torch.cuda.synchronize()
     L = _lib.lib()
     SS, MS = L.mpcqp_state_stride(N), L.mpcqp_model_stride(N)
-    st = _d2h(L.mpcqp_state_buffer(ctrl._ws), np.zeros((64, SS)))
-    model = _d2h(L.mpcqp_model_buffer(ctrl._ws), np.zeros((64, MS)))
+    st = d2h(L.mpcqp_state_buffer(ctrl._ws), np.zeros((64, SS)))
+    model = d2h(L.mpcqp_model_buffer(ctrl._ws), np.zeros((64, MS)))
     ref = cpu_solver.cpu_state(params, model, SS)
     n = 2 * N
     lane_off = (4 * N * N + 7) // 8 * 8
     P_gpu, P_cpu = st[:, : n * n], ref[:, : n * n]
-    assert _rel(P_gpu, P_cpu) <= 1e-12
+    assert rel(P_gpu, P_cpu) <= 1e-12
     for f, name in enumerate(["q", "D", "x", "E0", "E1", "E2", "lo0", "lo1", "lo2", "hi0", "hi1", "hi2",
                               "w0", "w1", "w2"]):
         if name == "x":
             continue
         g = st[:, lane_off + 64 * f: lane_off + 64 * (f + 1)]
         c = ref[:, lane_off + 64 * f: lane_off + 64 * (f + 1)]
-        assert _rel(g, c) <= 1e-12, name
-    assert _rel(st[:, lane_off + 15 * 64], ref[:, lane_off + 15 * 64]) <= 1e-12
+        assert rel(g, c) <= 1e-12, name
+    assert rel(st[:, lane_off + 15 * 64], ref[:, lane_off + 15 * 64]) <= 1e-12
     ctrl.close()
 
 
@@ -434,11 +367,11 @@ def test_admm_iterate_matches_restatement(cuda):
     from mpcqp import scenarios
 
     batch = scenarios.config3(256)
-    params = _params(20)
-    out = _solve(params, batch.x0, batch.ref, batch.u_prev, polish=0)
+    params = base_params(20)
+    out = solve(params, batch.x0, batch.ref, batch.u_prev, polish=0)
     ref = cpu_solver.cpu_solve(params, batch.x0, batch.ref, batch.u_prev, polish=0)
     same = out["iters"][:, 0] == ref["iters"][:, 0]
     assert same.mean() >= 0.95, same.mean()
     # the ADMM iterate is only eps_abs = eps_rel = 1e-3 accurate by construction and ~100
     # iterations amplify the rounding differences of tree vs sequential sums to ~1e-6
-    assert _rel(out["U"][same], ref["U"][same]) <= 1e-4
+    assert rel(out["U"][same], ref["U"][same]) <= 1e-4

@@ -7,6 +7,7 @@ from types import SimpleNamespace
 
 import numpy as np
 import pytest
+from gpu_helpers import base_params, default_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -28,9 +29,9 @@ def test_mpc_controller_reference_test_case(cuda):
     np.testing.assert_allclose(Xp[:, 0], x0)
 
 
-def _default_plan(golden):
-    g = golden("default_plan.npz")
-    planning = SimpleNamespace(plan=SimpleNamespace(success=True, path=[tuple(map(float, p)) for p in g["path"]]))
+def _planning_and_maps(golden):
+    g, path = default_plan(golden)
+    planning = SimpleNamespace(plan=SimpleNamespace(success=True, path=path))
     maps = SimpleNamespace(start=tuple(g["start"]), goal=tuple(g["goal"]))
     return g, planning, maps
 
@@ -46,7 +47,7 @@ def test_tracker_reproduces_reference_closed_loop(cuda, golden, N, sim_steps, se
     from mpcqp.config import MPCConfig, VizConfig
     from mpcqp.pipeline.control_stage import TrajectoryTracker
 
-    g, planning, maps = _default_plan(golden)
+    g, planning, maps = _planning_and_maps(golden)
     loop = golden("closed_loop.npz")
     tracker = TrajectoryTracker(MPCConfig(horizon=N, sim_steps=sim_steps), VizConfig(),
                                 solver_settings=dict(settings), relaxed_solver_settings=dict(settings))
@@ -112,11 +113,10 @@ def test_batched_controller_reuses_device_inputs(cuda):
     the device."""
     import torch
     from mpcqp import scenarios
-    from mpcqp.config import MPCConfig
     from mpcqp.control.mpc_controller import BatchedMPCController
 
     b = scenarios.config3(128)
-    ctrl = BatchedMPCController(MPCConfig(horizon=20).to_parameters(0.8), 128, device="cuda:0")
+    ctrl = BatchedMPCController(base_params(20), 128, device="cuda:0")
     x0 = torch.from_numpy(b.x0).to(cuda)
     ref = torch.from_numpy(b.ref).to(cuda)
     up = torch.from_numpy(b.u_prev).to(cuda)
@@ -135,7 +135,6 @@ def test_solve_one_equals_solve_batch(cuda):
     mpcqp_solve_staged: the kernels read and write the workspace's mapped host blocks in place,
     on its private stream), with windows longer than N + 1 rows and u_prev omitted."""
     from mpcqp import _lib, scenarios
-    from mpcqp.config import MPCConfig
     from mpcqp.control.mpc_controller import BatchedMPCController
 
     for N in (20, 40):
@@ -144,7 +143,7 @@ def test_solve_one_equals_solve_batch(cuda):
         ref[3, 2:, 0] = np.nan  # status numerical_error
         up = b.u_prev.copy()
         up[4] = 0.0
-        ctrl = BatchedMPCController(MPCConfig(horizon=N).to_parameters(0.8), 5, device="cuda:0")
+        ctrl = BatchedMPCController(base_params(N), 5, device="cuda:0")
         sol = ctrl.solve_batch(b.x0, ref, up)
         st, U, X = sol.status.cpu().numpy(), sol.U.cpu().numpy(), sol.X.cpu().numpy()
         for q in range(5):
@@ -165,12 +164,11 @@ def test_drop_in_unpolished_result_is_osqp_scaled(cuda):
     build's one-pass default.  A polished QP returns the exact optimum, which no scaling
     changes.  With the polish off, every drop-in solve runs OSQP's 10 passes."""
     from mpcqp import _lib, scenarios
-    from mpcqp.config import MPCConfig
     from mpcqp.control.mpc_controller import BatchedMPCController, MPCController
 
     N = 15
     b = scenarios.config3(24, horizon=N, seed=3)
-    params = MPCConfig(horizon=N).to_parameters(0.8)
+    params = base_params(N)
     for capped in (dict(max_iter=50, polish_from=0, polish_near=0.0),
                    dict(max_iter=50, polish=0, polish_from=0, polish_near=0.0)):
         res = {}
@@ -204,11 +202,10 @@ def test_b1_server_matches_launch_per_call(cuda, monkeypatch):
     import time
 
     from mpcqp import scenarios
-    from mpcqp.config import MPCConfig
     from mpcqp.control.mpc_controller import BatchedMPCController
 
     b = scenarios.config3(12, horizon=15, seed=41)
-    params = MPCConfig(horizon=15).to_parameters(0.8)
+    params = base_params(15)
     res = {}
     for mode in ("0", "1"):
         monkeypatch.setenv("MPCQP_B1_SERVER", mode)

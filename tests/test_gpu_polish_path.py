@@ -19,44 +19,25 @@ from __future__ import annotations
 
 import numpy as np
 import pytest
+from gpu_helpers import REL_TOL, base_params, controller, d2h, rel, take
 
 pytestmark = pytest.mark.gpu
 
-REL_TOL = 1e-8  # tests/test_gpu_parity.py, against the same oracle
 B = 256
-
-
-def _rel(a, b):
-    return float(np.abs(a - b).max() / max(1.0, np.abs(b).max()))
-
-
-def _d2h(ptr, host):
-    import ctypes
-
-    hip = ctypes.CDLL("libamdhip64.so")
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    hip.hipDeviceSynchronize()
-    assert hip.hipMemcpy(host.ctypes.data, ptr, host.nbytes, 2) == 0
-    return host
 
 
 def _solve_debug(N, x0, ref, u_prev):
     """(outputs, summed rank-1 counter) of one debug_state solve; the C restatement of the same batch."""
     import cpu_solver
-    import torch
     from mpcqp import _lib
-    from mpcqp.config import MPCConfig
-    from mpcqp.control.mpc_controller import BatchedMPCController
 
-    params = MPCConfig(horizon=N).to_parameters(0.8)
+    params = base_params(N)
     n = len(x0)
-    ctrl = BatchedMPCController(params, n, device="cuda:0", debug_state=1)
-    sol = ctrl.solve_batch(x0, ref, u_prev)
-    torch.cuda.synchronize()
-    out = {k: getattr(sol, k).cpu().numpy().copy() for k in sol._fields}
+    ctrl = controller(params, n, debug_state=1)
+    out = take(ctrl.solve_batch(x0, ref, u_prev))
     L = _lib.lib()
     SS = L.mpcqp_state_stride(N)
-    st = _d2h(L.mpcqp_state_buffer(ctrl._ws), np.zeros((n, SS)))
+    st = d2h(L.mpcqp_state_buffer(ctrl._ws), np.zeros((n, SS)))
     ctrl.close()
     n_r1 = st[:, SS - 8 + 6]  # debug scalar 6: the polish's rank-1 updates
     assert np.array_equal(n_r1, np.round(n_r1)) and (n_r1 >= 0).all()
@@ -69,7 +50,7 @@ def _assert_same_as_restatement(out, cpu):
     assert same.all(), f"QPs {np.flatnonzero(~same)[:10]} disagree on the counters"
     assert np.array_equal(out["status"], cpu["status"])
     assert np.array_equal(out["active"], cpu["active"])
-    assert _rel(out["U"], cpu["U"]) <= REL_TOL
+    assert rel(out["U"], cpu["U"]) <= REL_TOL
 
 
 @pytest.mark.parametrize("N", [3, 8, 9, 16, 17, 20, 23, 24, 32])

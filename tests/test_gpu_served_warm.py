@@ -19,89 +19,39 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 import warm_newton as wn
+from gpu_helpers import (ATOL, E_HORIZON, E_STATE, OUTS, assert_exact, assert_same, base_params, config3_case, controller,
+                         golden_case, is_live, take)
 
 pytestmark = pytest.mark.gpu
-
-REL_TOL = 1e-8  # the project's tolerance against the exact oracle (test_gpu_params.py)
-ATOL = 1e-7     # closed-loop states against the golden loop (test_gpu_pipeline.py)
-E_HORIZON, E_STATE = -2, -5
-_OUTS = ("u0", "X", "U", "status", "iters", "active")
-
-
-def _base(N, res=0.8):
-    from mpcqp.config import MPCConfig
-
-    return MPCConfig(horizon=N).to_parameters(res)
-
-
-def _controller(params, B=1, **kw):
-    from mpcqp.control.mpc_controller import BatchedMPCController
-
-    return BatchedMPCController(params, B, device="cuda:0", **kw)
-
-
-def _rel(a, b):
-    return float(np.abs(a - b).max() / max(1.0, np.abs(b).max()))
-
 
 def _one(ctrl, case, k, guess=None, passes=None):
     """All six outputs of one B = 1 solve of the case's QP k (from `guess` when given)."""
     kw = {} if guess is None else dict(U_guess=guess, guess_passes=passes)
     ctrl.solve_one(case["x0"][k], case["ref"][k], case["u_prev"][k], **kw)
-    out = {n: ctrl._one[n].copy() for n in _OUTS}
+    out = {n: ctrl._one[n].copy() for n in OUTS}
     assert np.array_equal(out["iters"], ctrl.last_iters)
     return out
 
 
-def _assert_same(got, want, what, names=_OUTS):
-    for n in names:
-        np.testing.assert_array_equal(np.ravel(got[n]), np.ravel(want[n]), err_msg=f"{what}: {n}")
+def _shifted_golden_case(golden, N):
+    """gpu_helpers.golden_case with the guesses a closed loop carries (``shifted``) as the case's guesses."""
+    case = golden_case(golden, N)
+    return dict(case, guesses=case["shifted"])
 
 
-def _live(ctrl) -> bool:
-    return ctrl._L.mpcqp_debug_serve_fault(ctrl._ws, 3) == 1
-
-
-_CASES = {}
-
-
-def _golden_case(golden, N):
-    if ("golden", N) not in _CASES:
-        params = _base(N, float(golden("default_plan.npz")["map_resolution"]))
-        w = wn.golden_windows(golden("closed_loop.npz"), params, N)
-        _CASES[("golden", N)] = dict(params=params, x0=w["x0"], ref=w["window"], u_prev=w["u_prev"], exact=w["exact"],
-                                     guesses=w["guesses"], shifted_runs=w["shifted_runs"])
-    return _CASES[("golden", N)]
-
-
-def _config3_case(N, B=4):
-    """B QPs of the config-3 generator at horizon N, each with its exact optimum as the guess."""
-    import mpc_oracle as mo
-    from mpcqp import scenarios
-
-    if ("config3", N) not in _CASES:
-        params = _base(N)
-        batch = scenarios.config3(B, horizon=N, seed=6100 + N)
-        exact = [mo.solve_exact(params, batch.x0[b], batch.ref[b], batch.u_prev[b]) for b in range(B)]
-        _CASES[("config3", N)] = dict(params=params, x0=batch.x0, ref=batch.ref, u_prev=batch.u_prev, exact=exact,
-                                      guesses=np.stack([e.Umat for e in exact]))
-    return _CASES[("config3", N)]
+_BATCH = {}
 
 
 def _batch(case, passes, key):
     """The batch API's answers for the whole case: mpcqp_solve_warm from the case's guesses
     (`passes` not None) or the cold mpcqp_solve; computed once per session."""
-    import torch
-
-    k = (key, "batch", passes)
-    if k not in _CASES:
-        ctrl = _controller(case["params"], len(case["x0"]))
+    k = (key, passes)
+    if k not in _BATCH:
+        ctrl = controller(case["params"], len(case["x0"]))
         kw = {} if passes is None else dict(U_guess=case["guesses"], guess_passes=passes)
-        sol = ctrl.solve_batch(case["x0"], case["ref"], case["u_prev"], **kw)
-        torch.cuda.synchronize()
-        _CASES[k] = {n: getattr(sol, n).cpu().numpy().copy() for n in _OUTS}
+        _BATCH[k] = take(ctrl.solve_batch(case["x0"], case["ref"], case["u_prev"], **kw))
         ctrl.close()
-    return _CASES[k]
+    return _BATCH[k]
 
 
 # ---------------------------------------------------------------------- 1. served = staged = batch
@@ -112,16 +62,16 @@ def test_b1_warm_equals_the_batch_warm_solve_on_the_golden_windows(cuda, golden,
     from window k - 1's optimum, shifted), with 1 and 8 passes: the launched (MPCQP_B1_SERVER=0) and the
     served B = 1 warm calls return mpcqp_solve_warm's outputs bit for bit, the counters included."""
     monkeypatch.setenv("MPCQP_B1_SERVER", mode)
-    case = _golden_case(golden, N)
-    ctrl = _controller(case["params"])
+    case = _shifted_golden_case(golden, N)
+    ctrl = controller(case["params"], 1)
     hits = {}
     for passes in (1, 8):
         want = _batch(case, passes, ("golden", N))
         for k in range(len(case["x0"])):
             got = _one(ctrl, case, k, case["guesses"][k], passes)
-            _assert_same(got, {n: want[n][k] for n in _OUTS}, f"N={N} mode {mode} passes {passes} window {k}")
+            assert_same(got, {n: want[n][k] for n in OUTS}, f"N={N} mode {mode} passes {passes} window {k}")
         hits[passes] = int((want["iters"][:, 0] == 0).sum())
-    assert _live(ctrl) == (mode == "1")
+    assert is_live(ctrl) == (mode == "1")
     ctrl.close()
     print(f"N={N} mode {mode}: hits of 65 by passes {hits}")
 
@@ -130,14 +80,14 @@ def test_b1_warm_equals_the_batch_warm_solve_on_the_golden_windows(cuda, golden,
 def test_b1_warm_equals_the_batch_warm_solve_from_exact_guesses(cuda, monkeypatch, N):
     """Exact guesses at N = 1 (nothing to shift), 16 (past the pair limit), 24 (packed Pbar), 29 (the
     spill range) and 32 (every lane a column), both B = 1 calls against the batch warm solve."""
-    case = _config3_case(N)
+    case = config3_case(N, 4, 6100 + N)
     want = _batch(case, 2, ("config3", N))
     for mode in ("0", "1"):
         monkeypatch.setenv("MPCQP_B1_SERVER", mode)
-        ctrl = _controller(case["params"])
+        ctrl = controller(case["params"], 1)
         for k in range(len(case["x0"])):
             got = _one(ctrl, case, k, case["guesses"][k], 2)
-            _assert_same(got, {n: want[n][k] for n in _OUTS}, f"N={N} mode {mode} QP {k}")
+            assert_same(got, {n: want[n][k] for n in OUTS}, f"N={N} mode {mode} QP {k}")
         ctrl.close()
     assert (want["status"] == 1).all()
 
@@ -151,7 +101,7 @@ def _raw(ctrl, case, k, call, *args):
     io["up"][:] = case["u_prev"][k]
     rc = getattr(ctrl._L, call)(ctrl._ws, *args)
     assert rc == 0, (call, rc, ctrl._L.mpcqp_last_error())
-    return {n: io[n].copy() for n in _OUTS}
+    return {n: io[n].copy() for n in OUTS}
 
 
 @pytest.mark.parametrize("mode", ["0", "1"])
@@ -160,10 +110,10 @@ def test_unusable_guess_is_the_cold_b1_solve_bit_for_bit(cuda, golden, monkeypat
     included, is the cold call's (mpcqp_solve_served / mpcqp_solve_staged) of the same QP."""
     monkeypatch.setenv("MPCQP_B1_SERVER", mode)
     N = 10
-    case = _golden_case(golden, N)
+    case = _shifted_golden_case(golden, N)
     cold_call, warm_call = (("mpcqp_solve_staged", "mpcqp_solve_staged_warm") if mode == "0"
                             else ("mpcqp_solve_served", "mpcqp_solve_served_warm"))
-    ctrl = _controller(case["params"])
+    ctrl = controller(case["params"], 1)
     ctrl._one = ctrl._stage()
     rows = (0, 7, 30, 64)
     cold = {k: _raw(ctrl, case, k, cold_call) for k in rows}
@@ -171,13 +121,13 @@ def test_unusable_guess_is_the_cold_b1_solve_bit_for_bit(cuda, golden, monkeypat
     block = ctrl._stage_guess()
     assert block.shape == (2, N) and np.isnan(block).all()  # fresh: NaN, so a solve before any write is cold
     for k in rows:
-        _assert_same(_raw(ctrl, case, k, warm_call, 8), cold[k], f"fresh block, window {k}")
+        assert_same(_raw(ctrl, case, k, warm_call, 8), cold[k], f"fresh block, window {k}")
     for k in rows:
         g = case["exact"][k].Umat.copy()
         g[1, N - 1] = np.nan  # the last steering angle
-        _assert_same(_one(ctrl, case, k, g, 8), cold[k], f"NaN entry, window {k}")
+        assert_same(_one(ctrl, case, k, g, 8), cold[k], f"NaN entry, window {k}")
         for passes in (0, -3):
-            _assert_same(_one(ctrl, case, k, case["exact"][k].Umat, passes), cold[k], f"passes {passes}, window {k}")
+            assert_same(_one(ctrl, case, k, case["exact"][k].Umat, passes), cold[k], f"passes {passes}, window {k}")
     # and the same block, usable: a hit
     out = _one(ctrl, case, rows[1], case["exact"][rows[1]].Umat, 8)
     assert out["status"][0] == 1 and out["iters"][0] == 0
@@ -188,19 +138,17 @@ def test_unusable_guess_is_the_cold_b1_solve_bit_for_bit(cuda, golden, monkeypat
 @pytest.mark.parametrize("N", [10, 15])
 def test_served_warm_hits_where_the_host_model_converges_in_one_pass(cuda, golden, monkeypatch, N):
     monkeypatch.setenv("MPCQP_B1_SERVER", "1")
-    case = _golden_case(golden, N)
+    case = _shifted_golden_case(golden, N)
     runs = case["shifted_runs"]
     expected = [k for k in range(1, len(runs)) if runs[k].passes == 1 and runs[k].margin > wn.MARGIN]
     assert len(expected) >= 25
-    ctrl = _controller(case["params"])
+    ctrl = controller(case["params"], 1)
     for k in expected:
         out = _one(ctrl, case, k, case["guesses"][k])
         ex = case["exact"][k]
         assert out["status"][0] == 1, (N, k, out["status"])
         assert out["iters"][0] == 0 and out["iters"][1] == 1, (N, k, out["iters"])
-        e = max(_rel(out["U"], ex.Umat), _rel(out["X"], ex.X), _rel(out["u0"], ex.Umat[:, 0]))
-        assert e <= REL_TOL, f"N={N} window {k}: rel err {e:.3e}"
-        assert np.array_equal(out["active"], ex.active), (N, k)
+        assert_exact(out, None, ex, f"N={N} window {k}", solved=True)
     ctrl.close()
 
 
@@ -239,7 +187,7 @@ def test_warm_tracker_reproduces_the_reference_closed_loop(cuda, golden, N, sim_
 def _launched(case, rows, monkeypatch):
     """The launched counterparts (MPCQP_B1_SERVER=0) of the rows' cold and warm (exact guess, 2 passes) solves."""
     monkeypatch.setenv("MPCQP_B1_SERVER", "0")
-    ctrl = _controller(case["params"])
+    ctrl = controller(case["params"], 1)
     cold = {k: _one(ctrl, case, k) for k in rows}
     warm = {k: _one(ctrl, case, k, case["guesses"][k], 2) for k in rows}
     ctrl.close()
@@ -250,25 +198,25 @@ def _launched(case, rows, monkeypatch):
 def test_cold_and_warm_served_calls_alternate_on_one_workspace(cuda, monkeypatch):
     """A workspace has one resident wave, of the kind of its last served call: every answer equals its
     launched counterpart, whichever kind served before."""
-    case = _config3_case(16)
+    case = config3_case(16, 4, 6100 + 16)
     rows = range(len(case["x0"]))
     cold, warm = _launched(case, rows, monkeypatch)
-    ctrl = _controller(case["params"])
+    ctrl = controller(case["params"], 1)
     for rep, kinds in enumerate(("cw", "wc", "wwcc")):
         for i, kind in enumerate(kinds * 2):
             k = (rep + i) % len(case["x0"])
             if kind == "c":
-                _assert_same(_one(ctrl, case, k), cold[k], f"cold {rep}.{i}")
+                assert_same(_one(ctrl, case, k), cold[k], f"cold {rep}.{i}")
             else:
-                _assert_same(_one(ctrl, case, k, case["guesses"][k], 2), warm[k], f"warm {rep}.{i}")
-            assert _live(ctrl)
+                assert_same(_one(ctrl, case, k, case["guesses"][k], 2), warm[k], f"warm {rep}.{i}")
+            assert is_live(ctrl)
     assert all(warm[k]["iters"][0] == 0 for k in rows) and all(cold[k]["iters"][0] > 0 for k in rows)
     ctrl.close()
 
 
 def test_two_workspaces_alternate_warm_calls(cuda, monkeypatch):
     """The drop-in's nominal and relaxed workspaces, both warm: a switch stops the other workspace's wave."""
-    case = _config3_case(16)
+    case = config3_case(16, 4, 6100 + 16)
     nominal = case["params"]
     du = nominal.du_bounds
     relaxed = dataclasses.replace(nominal, du_bounds=((du[0][0] - 5.0, du[0][1] + 5.0),
@@ -276,11 +224,11 @@ def test_two_workspaces_alternate_warm_calls(cuda, monkeypatch):
     cases = [case, dict(case, params=relaxed)]
     rows = range(len(case["x0"]))
     want = [_launched(c, rows, monkeypatch)[1] for c in cases]
-    ctrls = [_controller(c["params"]) for c in cases]
+    ctrls = [controller(c["params"], 1) for c in cases]
     for i in range(12):
         w, k = i % 2 if i % 5 else 0, i % len(case["x0"])
-        _assert_same(_one(ctrls[w], cases[w], k, case["guesses"][k], 2), want[w][k], f"call {i} workspace {w}")
-        live = [_live(c) for c in ctrls]
+        assert_same(_one(ctrls[w], cases[w], k, case["guesses"][k], 2), want[w][k], f"call {i} workspace {w}")
+        live = [is_live(c) for c in ctrls]
         assert live[w] and sum(live) == 1, (i, live)
     for c in ctrls:
         c.close()
@@ -291,19 +239,19 @@ def test_served_warm_failure_paths_and_set_params(cuda, monkeypatch):
     warm call (LibraryError) and the next one succeeds; mpcqp_set_params between warm calls stops the wave."""
     from mpcqp import _lib
 
-    case = _config3_case(16)
+    case = config3_case(16, 4, 6100 + 16)
     rows = range(len(case["x0"]))
     _, warm = _launched(case, rows, monkeypatch)
-    ctrl = _controller(case["params"])
+    ctrl = controller(case["params"], 1)
     L = ctrl._L
 
     def check(k):
-        _assert_same(_one(ctrl, case, k, case["guesses"][k], 2), warm[k], f"QP {k}")
-        assert _live(ctrl)
+        assert_same(_one(ctrl, case, k, case["guesses"][k], 2), warm[k], f"QP {k}")
+        assert is_live(ctrl)
 
     check(0)
     assert L.mpcqp_debug_serve_fault(ctrl._ws, 2) == 0  # the wave leaves; the host still believes it resident
-    assert _live(ctrl)
+    assert is_live(ctrl)
     check(1)
     assert L.mpcqp_debug_serve_fault(ctrl._ws, 2) == 0
     assert L.mpcqp_debug_serve_fault(ctrl._ws, 1) == 0
@@ -311,7 +259,7 @@ def test_served_warm_failure_paths_and_set_params(cuda, monkeypatch):
         _one(ctrl, case, 2, case["guesses"][2], 2)
     check(2)
     ctrl.set_params(case["params"])
-    assert not _live(ctrl)
+    assert not is_live(ctrl)
     check(3)
     ctrl.close()
 
@@ -323,7 +271,8 @@ def test_b1_warm_refusals_write_nothing(cuda, how):
 
     N = 40 if how == "n40" else 10
     b = scenarios.config3(1, horizon=N, seed=11)
-    ctrl = _controller(_base(N), **{"reproducible": dict(reproducible=1), "debug_state": dict(debug_state=1)}.get(how, {}))
+    ctrl = controller(base_params(N), 1,
+                      **{"reproducible": dict(reproducible=1), "debug_state": dict(debug_state=1)}.get(how, {}))
     io = ctrl._one = ctrl._stage()
     if how != "no_guess_block":
         ctrl._stage_guess()[:] = 0.0
@@ -333,14 +282,14 @@ def test_b1_warm_refusals_write_nothing(cuda, how):
     for call in ("mpcqp_solve_staged_warm", "mpcqp_solve_served_warm"):
         assert getattr(ctrl._L, call)(ctrl._ws, 2) == want, (how, call, ctrl._L.mpcqp_last_error())
         assert io["status"][0] == 77
-        assert not _live(ctrl)
+        assert not is_live(ctrl)
     assert ctrl._L.mpcqp_solve_served(ctrl._ws) == 0  # the cold call still runs on this workspace
     assert io["status"][0] != 77
     ctrl.close()
 
 
 def test_stage_guess_needs_the_staging_blocks(cuda):
-    ctrl = _controller(_base(10))
+    ctrl = controller(base_params(10), 1)
     g = ctypes.c_void_p(77)
     assert ctrl._L.mpcqp_stage_guess(ctrl._ws, ctypes.byref(g)) == E_STATE
     assert g.value == 77

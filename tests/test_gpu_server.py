@@ -9,14 +9,9 @@ import time
 
 import numpy as np
 import pytest
+from gpu_helpers import base_params, is_live
 
 pytestmark = pytest.mark.gpu
-
-
-def _live(ctrl) -> bool:
-    from mpcqp import _lib
-
-    return _lib.lib().mpcqp_debug_serve_fault(ctrl._ws, 3) == 1
 
 
 def _solve_all(ctrls, b, order):
@@ -30,12 +25,11 @@ def test_one_resident_server_while_alternating_workspaces(cuda, monkeypatch):
     import dataclasses
 
     from mpcqp import scenarios
-    from mpcqp.config import MPCConfig
     from mpcqp.control.mpc_controller import BatchedMPCController
 
     N = 15
     b = scenarios.config3(30, horizon=N, seed=17)
-    nominal = MPCConfig(horizon=N).to_parameters(0.8)
+    nominal = base_params(N)
     du = nominal.du_bounds  # the relaxed retry's parameter block (control_stage.py:45-49)
     relaxed = dataclasses.replace(nominal, du_bounds=((du[0][0] - 5.0, du[0][1] + 5.0),
                                                       (du[1][0] - 0.05, du[1][1] + 0.05)))
@@ -54,7 +48,7 @@ def test_one_resident_server_while_alternating_workspaces(cuda, monkeypatch):
             out.append(ctrls[k].solve_one(b.x0[q], b.ref[q], b.u_prev[q]))
             worst = max(worst, time.perf_counter() - t)
             if mode == "1":
-                live = [_live(c) for c in ctrls]
+                live = [is_live(c) for c in ctrls]
                 assert live[k] and sum(live) == 1, (q, live)
         res[mode] = out
         # a switch costs a stop and a launch, never another wave's 2 ms idle exit
@@ -76,7 +70,6 @@ def test_server_does_not_hold_default_priority_streams(cuda):
     import torch
 
     from mpcqp import scenarios
-    from mpcqp.config import MPCConfig
     from mpcqp.control.mpc_controller import BatchedMPCController
 
     b = scenarios.config3(8, horizon=10, seed=3)
@@ -86,9 +79,9 @@ def test_server_does_not_hold_default_priority_streams(cuda):
         with torch.cuda.stream(s):
             x[i].add_(-1.0)
     torch.cuda.synchronize()
-    ctrl = BatchedMPCController(MPCConfig(horizon=10).to_parameters(0.8), 1, device="cuda:0")
+    ctrl = BatchedMPCController(base_params(10), 1, device="cuda:0")
     ctrl.solve_one(b.x0[0], b.ref[0], b.u_prev[0])
-    assert _live(ctrl)
+    assert is_live(ctrl)
     evs = []
     t0 = time.perf_counter()
     for i, s in enumerate(streams):
@@ -106,7 +99,7 @@ def test_server_does_not_hold_default_priority_streams(cuda):
         for i, e in enumerate(evs):
             if i not in done and e.query():
                 done[i] = time.perf_counter() - t0
-    assert _live(ctrl)
+    assert is_live(ctrl)
     assert len(done) == 8, f"streams still blocked after 50 ms of served requests: {sorted(set(range(8)) - set(done))}"
     assert max(done.values()) < 0.01, done
     torch.cuda.synchronize()
@@ -120,14 +113,13 @@ def test_server_failure_paths(cuda, monkeypatch):
     (None, None, None)) and the next call launches again; a non-finite input returns status -10 next
     to a live server and the following QP is solved normally."""
     from mpcqp import _lib, scenarios
-    from mpcqp.config import MPCConfig
     from mpcqp.control import mpc_controller as mc
     from mpcqp.control.mpc_controller import BatchedMPCController
 
     monkeypatch.setenv("MPCQP_B1_SERVER", "1")
     N = 10
     b = scenarios.config3(6, horizon=N, seed=5)
-    params = MPCConfig(horizon=N).to_parameters(0.8)
+    params = base_params(N)
     ref_c = BatchedMPCController(params, 6, device="cuda:0")
     sol = ref_c.solve_batch(b.x0, b.ref, b.u_prev)
     exp_st, exp_U = sol.status.cpu().numpy().copy(), sol.U.cpu().numpy().copy()
@@ -141,12 +133,12 @@ def test_server_failure_paths(cuda, monkeypatch):
         assert st == 1 and np.array_equal(U, exp_U[q]), q
 
     check(0)
-    assert _live(ctrl)
+    assert is_live(ctrl)
     # 1. the wave leaves unannounced: the host still believes it resident
     assert L.mpcqp_debug_serve_fault(ctrl._ws, 2) == 0
-    assert _live(ctrl)
+    assert is_live(ctrl)
     check(1)
-    assert _live(ctrl)
+    assert is_live(ctrl)
     # 2. a refused launch (after the wave is gone): the call fails, the next one launches again
     assert L.mpcqp_debug_serve_fault(ctrl._ws, 2) == 0
     assert L.mpcqp_debug_serve_fault(ctrl._ws, 1) == 0
@@ -158,7 +150,7 @@ def test_server_failure_paths(cuda, monkeypatch):
     x0[1] = np.nan
     st, *_ = ctrl.solve_one(x0, b.ref[3], b.u_prev[3])
     assert st == _lib.NUMERICAL_ERROR
-    assert _live(ctrl)
+    assert is_live(ctrl)
     check(3)
     check(4)
     # the drop-in maps a refused launch to (None, None, None)
@@ -179,7 +171,6 @@ def test_served_unpolished_and_nan_against_launch(cuda, monkeypatch, capped):
     the served path against a launch per call: statuses, the four counters and U equal bit for bit
     (the kernels contract multiply-adds only within a source expression)."""
     from mpcqp import _lib, scenarios
-    from mpcqp.config import MPCConfig
     from mpcqp.control.mpc_controller import BatchedMPCController
 
     N = 20
@@ -187,7 +178,7 @@ def test_served_unpolished_and_nan_against_launch(cuda, monkeypatch, capped):
     x0 = b.x0.copy()
     x0[5, 0] = np.nan
     x0[11, 3] = np.inf
-    params = MPCConfig(horizon=N).to_parameters(0.8)
+    params = base_params(N)
     res = {}
     for mode in ("0", "1"):
         monkeypatch.setenv("MPCQP_B1_SERVER", mode)
@@ -216,13 +207,12 @@ def test_two_threads_on_two_workspaces(cuda, monkeypatch):
     import threading
 
     from mpcqp import scenarios
-    from mpcqp.config import MPCConfig
     from mpcqp.control.mpc_controller import BatchedMPCController
 
     monkeypatch.setenv("MPCQP_B1_SERVER", "1")
     N, Q = 10, 60
     b = scenarios.config3(Q, horizon=N, seed=23)
-    params = MPCConfig(horizon=N).to_parameters(0.8)
+    params = base_params(N)
     ref_c = BatchedMPCController(params, Q, device="cuda:0")
     sol = ref_c.solve_batch(b.x0, b.ref, b.u_prev)
     exp_st, exp_U = sol.status.cpu().numpy().copy(), sol.U.cpu().numpy().copy()

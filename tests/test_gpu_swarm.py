@@ -16,36 +16,9 @@ from types import SimpleNamespace
 
 import numpy as np
 import pytest
+from gpu_helpers import SWARM_HORIZON as N_HORIZON, oracle_plan, pairs, planner_params, swarm
 
 pytestmark = pytest.mark.gpu
-
-N_HORIZON = 15
-
-
-def _pairs(occ, V, seed):
-    rng = np.random.default_rng(seed)
-    free = np.argwhere(occ == 1)
-    starts, goals = [], []
-    while len(starts) < V:
-        a, b = free[rng.integers(0, len(free), 2)]
-        if np.hypot(*(a - b)) > 30:  # keep the trips non-trivial
-            starts.append(a[::-1].astype(float))
-            goals.append(b[::-1].astype(float))
-    return np.array(starts), np.array(goals)
-
-
-def _planner_params(seed=13):
-    from mpcqp.planning.rrt_star import default_planner_parameters
-
-    return default_planner_parameters(max_iterations=1500, random_seed=int(seed))
-
-
-def _swarm(occ, V, sim_steps, **kw):
-    from mpcqp.config import MPCConfig
-    from mpcqp.pipeline.swarm import Swarm
-
-    return Swarm(occ, MPCConfig(horizon=N_HORIZON, sim_steps=sim_steps), _planner_params(),
-                 map_resolution=0.8, max_vehicles=V, device="cuda:0", **kw)
 
 
 def _c_solve(params, state, window, u_prev):
@@ -87,37 +60,8 @@ def _host_continue(state, u_prev, path, goal, steps):
     return np.asarray(mo.track_from(_oracle_params(), ref, state, u_prev, goal, steps, solve_fn=_c_solve))
 
 
-def _oracle_plan(occ, start, goal, seed, cr=False):
-    """RRTStarPlanner.plan (rrt_star.py:201-283) on the host: oracle/rrt_oracle.grow_tree fed the
-    seed's own sample stream (draw_samples), oracle extraction and shortcut pruning, then the
-    Catmull-Rom smoothing of the host restatement (pinned by branches.npz).  cr: the steer's
-    trig correctly rounded (the device's) instead of glibc's."""
-    import rrt_oracle as ro
-    from mpcqp.common.geometry import catmull_rom_spline
-    from mpcqp.planning.rrt_star import draw_samples
-
-    prm = _planner_params(seed)
-    smp = draw_samples(int(seed), goal, occ.shape, prm.goal_sample_rate, prm.max_iterations)
-    nodes, _, gi = ro.grow_tree(occ, start, goal, smp, step=prm.step, goal_radius=prm.goal_radius,
-                                rewire_radius=prm.rewire_radius, collision_step=prm.collision_step,
-                                trig=ro.CR_TRIG if cr else ro.LIBM_TRIG)
-    if gi < 0:
-        return None
-    path = ro.extract_path(nodes, gi)
-    if prm.prune_path and len(path) >= 2:
-        pruned = ro.shortcut_prune(occ, path, prm.collision_step)
-        if len(pruned) >= 2:
-            path = pruned
-    if len(path) >= 2 and prm.spline_samples > 1:
-        spline = catmull_rom_spline(path, samples_per_segment=prm.spline_samples, alpha=prm.spline_alpha,
-                                    dedupe_tol=prm.dedupe_tolerance)
-        if len(spline) >= 2:
-            path = [tuple(map(float, q)) for q in spline]
-    return path
-
-
 def _check_plan(occ, start, goal, seed, path, tol=1e-4):
-    """The device plan against the host restatement of the reference planner (_oracle_plan): same
+    """The device plan against the host restatement of the reference planner (oracle_plan): same
     number of points, coordinates within the ~1e-5 px the duplicated end knots amplify an ulp to
     (the trees themselves are bit-exact, test_gpu_planning.py).  Where the plan differs from the
     libm restatement's, it must be the plan with correctly rounded steer trig (glibc's rounding,
@@ -128,9 +72,9 @@ def _check_plan(occ, start, goal, seed, path, tol=1e-4):
         return plan is not None and np.asarray(plan).shape == got.shape and \
             np.abs(np.asarray(plan) - got).max() <= tol
 
-    if same(_oracle_plan(occ, start, goal, seed)):
+    if same(oracle_plan(occ, start, goal, seed)):
         return "libm"
-    plan = _oracle_plan(occ, start, goal, seed, cr=True)
+    plan = oracle_plan(occ, start, goal, seed, cr=True)
     assert plan is not None
     ref = np.asarray(plan)
     assert ref.shape == got.shape, (ref.shape, got.shape)
@@ -145,8 +89,8 @@ def test_device_smoothing_matches_reference_planner(cuda, golden):
     from mpcqp.planning.rrt_star import BatchedRRTStarPlanner
 
     occ = golden("default_plan.npz")["occupancy"]
-    starts, goals = _pairs(occ, 48, 3)
-    pl = BatchedRRTStarPlanner(occ, _planner_params(), device="cuda:0")
+    starts, goals = pairs(occ, 48, 3)
+    pl = BatchedRRTStarPlanner(occ, planner_params(), device="cuda:0")
     dev = pl.paths_batch(starts, goals, np.arange(48), smoothing="device")
     host = pl.paths_batch(starts, goals, np.arange(48), smoothing="host")
     assert sum(p is not None for p in dev) > 40
@@ -177,8 +121,8 @@ def test_swarm_vehicles_follow_the_reference_loop(cuda, golden):
 
     occ = golden("default_plan.npz")["occupancy"]
     V, steps = 24, 120
-    starts, goals = _pairs(occ, V, 1)
-    sw = _swarm(occ, V, steps, replan_distance=1e9)  # no off-track replans: the plain per-vehicle loop
+    starts, goals = pairs(occ, V, 1)
+    sw = swarm(occ, V, steps, replan_distance=1e9)  # no off-track replans: the plain per-vehicle loop
     res = sw.run(starts, goals, seeds=np.arange(V), check_every=20)
     assert (res.replans == 0).all()
     assert res.planned.mean() > 0.8
@@ -203,8 +147,8 @@ def test_per_step_replan_100_vehicles(cuda, golden):
 
     occ = golden("default_plan.npz")["occupancy"]
     V, steps = 100, 150
-    starts, goals = _pairs(occ, V, 7)
-    sw = _swarm(occ, V, steps, replan_distance=5.5, max_replans=1)
+    starts, goals = pairs(occ, V, 7)
+    sw = swarm(occ, V, steps, replan_distance=5.5, max_replans=1)
     res = sw.run(starts, goals, seeds=np.arange(V), check_every=25)
     replanned = np.flatnonzero(res.replans > 0)
     assert len(replanned) > 0, "the trigger never fired"
@@ -243,12 +187,12 @@ def test_sharded_swarm_equals_one_swarm(cuda, golden):
 
     occ = golden("default_plan.npz")["occupancy"]
     V, world = 40, 3
-    starts, goals = _pairs(occ, V, 21)
-    one = _swarm(occ, V, 200, replan_distance=2.5).run(starts, goals, seeds=np.arange(V), check_every=25)
+    starts, goals = pairs(occ, V, 21)
+    one = swarm(occ, V, 200, replan_distance=2.5).run(starts, goals, seeds=np.arange(V), check_every=25)
     shards = []
     for r in range(world):  # each "rank": its own Swarm sized to its block
         lo, hi = shard_vehicles(V, world, r)
-        sw = _swarm(occ, hi - lo, 200, replan_distance=2.5)
+        sw = swarm(occ, hi - lo, 200, replan_distance=2.5)
         shards.append(run_swarm_sharded(sw.run, starts, goals, np.arange(V), rank=r, world=world,
                                         all_gather_object=lambda out, obj, r=r: out.__setitem__(r, obj),
                                         check_every=25))
@@ -276,9 +220,9 @@ def test_fused_swarm_equals_stepped_swarm(cuda, golden, V, steps, dist, max_repl
     """mpcqp_swarm_loop (max_replans + 1 fused-loop launches, the trigger inside the loop) == the
     graph-stepped swarm (mpcqp_swarm_run): every vehicle's states, inputs, phase, steps, replans,
     replan steps, replan start and new plan identical bit for bit, with the trigger firing."""
-    starts, goals = _pairs(golden("default_plan.npz")["occupancy"], V, seed)
+    starts, goals = pairs(golden("default_plan.npz")["occupancy"], V, seed)
     occ = golden("default_plan.npz")["occupancy"]
-    res = [_swarm(occ, V, steps, replan_distance=dist, max_replans=max_replans, fused=fused)
+    res = [swarm(occ, V, steps, replan_distance=dist, max_replans=max_replans, fused=fused)
            .run(starts, goals, seeds=np.arange(V), check_every=25) for fused in (False, True)]
     a, b = res
     assert a.replans.sum() > 0, "the trigger should fire"

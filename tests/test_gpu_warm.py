@@ -15,77 +15,12 @@ import ctypes
 import numpy as np
 import pytest
 import warm_newton as wn
+from gpu_helpers import (ATOL, E_ARG, E_HORIZON, E_STATE, LOOP_BUFFERS_MASK, OUTS, assert_exact, base_params, config3_case,
+                         controller, default_plan, fleet_tracker, golden_case, loop_buffers, run_loop, take, varied_fleet)
 
 pytestmark = pytest.mark.gpu
 
-REL_TOL = 1e-8  # the project's tolerance against the exact oracle (test_gpu_params.py)
-ATOL = 1e-7     # closed-loop states against the golden loop (test_gpu_fleet.py)
-E_ARG, E_HORIZON, E_STATE = -1, -2, -5
-_OUTS = ("u0", "X", "U", "status", "iters", "active")
 _SAME = ("u0", "X", "U", "status", "active")
-_LOOP_BUFFERS = ("state", "u_prev", "path_idx", "phase", "steps", "trace", "u_trace", "X", "status", "u0", "mask")
-
-
-def _base(N, res=0.8):
-    from mpcqp.config import MPCConfig
-
-    return MPCConfig(horizon=N).to_parameters(res)
-
-
-def _controller(params, B, **kw):
-    from mpcqp.control.mpc_controller import BatchedMPCController
-
-    return BatchedMPCController(params, B, device="cuda:0", **kw)
-
-
-def _take(sol):
-    import torch
-
-    torch.cuda.synchronize()  # raises if a kernel of the launch faulted
-    return {k: getattr(sol, k).cpu().numpy().copy() for k in _OUTS}
-
-
-def _rel(a, b):
-    return float(np.abs(a - b).max() / max(1.0, np.abs(b).max()))
-
-
-_CASES = {}
-
-
-def _config3_case(N, B=16):
-    """B QPs of the config-3 generator at horizon N with their exact optima and margins (computed once).
-    The slack weights put an active row a few 1e-6 outside its bound, so a QP now and then has a row
-    within MARGIN of one; with these seeds the oracle finds at most one such QP in 16 at every horizon
-    used here (a property of the inputs alone)."""
-    import mpc_oracle as mo
-    from mpcqp import scenarios
-
-    if (N, B) not in _CASES:
-        params = _base(N)
-        batch = scenarios.config3(B, horizon=N, seed=5200 + N)
-        exact = [mo.solve_exact(params, batch.x0[b], batch.ref[b], batch.u_prev[b]) for b in range(B)]
-        assert all(e.converged for e in exact)
-        margins = np.array([wn.margin(mo.condense(params, batch.x0[b], batch.ref[b], batch.u_prev[b]), exact[b].U)
-                            for b in range(B)])
-        _CASES[(N, B)] = dict(params=params, x0=batch.x0, ref=batch.ref, u_prev=batch.u_prev, exact=exact,
-                              margins=margins, guesses=np.stack([e.Umat for e in exact]))
-    return _CASES[(N, B)]
-
-
-def _golden_case(golden, N):
-    res = float(golden("default_plan.npz")["map_resolution"])
-    params = _base(N, res)
-    w = wn.golden_windows(golden("closed_loop.npz"), params, N)
-    return dict(params=params, x0=w["x0"], ref=w["window"], u_prev=w["u_prev"], exact=w["exact"], margins=w["margins"],
-                guesses=np.stack([e.Umat for e in w["exact"]]), shifted=w["guesses"], shifted_runs=w["shifted_runs"])
-
-
-def _assert_oracle(out, case, b, what):
-    ex = case["exact"][b]
-    assert out["status"][b] == 1, (what, b, out["status"][b])
-    e = max(_rel(out["U"][b], ex.Umat), _rel(out["X"][b], ex.X), _rel(out["u0"][b], ex.Umat[:, 0]))
-    assert e <= REL_TOL, f"{what} QP {b}: rel err {e:.3e}"
-    assert np.array_equal(out["active"][b], ex.active), f"{what} QP {b}: active set differs"
 
 
 def _assert_miss(warm, cold, b, passes, what):
@@ -103,10 +38,10 @@ def _assert_miss(warm, cold, b, passes, what):
 def _solve_pair(case, guesses, passes=None, rows=None):
     """(warm, cold) outputs of one controller on the case's QPs (`rows`: a subset)."""
     rows = np.arange(len(case["x0"])) if rows is None else np.asarray(rows)
-    ctrl = _controller(case["params"], len(rows))
+    ctrl = controller(case["params"], len(rows))
     args = (case["x0"][rows], case["ref"][rows], case["u_prev"][rows])
-    warm = _take(ctrl.solve_batch(*args, U_guess=np.asarray(guesses)[rows], guess_passes=passes))
-    cold = _take(ctrl.solve_batch(*args))
+    warm = take(ctrl.solve_batch(*args, U_guess=np.asarray(guesses)[rows], guess_passes=passes))
+    cold = take(ctrl.solve_batch(*args))
     ctrl.close()
     return warm, cold
 
@@ -116,9 +51,9 @@ def _solve_pair(case, guesses, passes=None, rows=None):
 def test_exact_guess_hits(cuda, golden, N):
     """From the optimum itself the attempt converges at once: N = 1 (nothing to shift), 15 / 16 (the
     pair limit), 23 / 24 (kept model, packed Pbar), 29 (the spill range), 32 (every lane a column)."""
-    cases = [("config3", _config3_case(N))]
+    cases = [("config3", config3_case(N, 16, 5200 + N, margins=True))]
     if N in (10, 15):
-        cases.append(("golden", _golden_case(golden, N)))
+        cases.append(("golden", golden_case(golden, N)))
     for name, case in cases:
         B = len(case["x0"])
         warm, _ = _solve_pair(case, case["guesses"], passes=2)
@@ -126,7 +61,7 @@ def test_exact_guess_hits(cuda, golden, N):
         print(f"N={N} {name}: {int(clear.sum())} of {B} clear of their bounds; iters {warm['iters'].tolist()}")
         assert (~clear).sum() <= (0 if name == "golden" else B // 10)
         for b in range(B):
-            _assert_oracle(warm, case, b, f"N={N} {name}")
+            assert_exact(warm, b, case["exact"][b], f"N={N} {name}", solved=True)
             if clear[b]:
                 assert warm["iters"][b, 0] == 0, (N, name, b, warm["iters"][b])
                 assert 1 <= warm["iters"][b, 1] <= 2, (N, name, b, warm["iters"][b])
@@ -138,17 +73,16 @@ def test_shifted_guess_along_the_golden_loop(cuda, golden, N):
     """What a closed loop carries: window k starts from window k - 1's optimum, shifted one step."""
     from mpcqp import _lib
 
-    case = _golden_case(golden, N)
+    case = golden_case(golden, N)
     rows = np.arange(1, len(case["x0"]))
     warm, cold = _solve_pair(case, case["shifted"], rows=rows)
-    sub = dict(case, exact=[case["exact"][k] for k in rows])
     hits = warm["iters"][:, 0] == 0
     expected = np.array([r.passes == 1 and r.margin > wn.MARGIN for r in case["shifted_runs"][1:]])
     print(f"N={N}: {int(hits.sum())} hits of {len(rows)}, {int(expected.sum())} expected from the host model; "
           f"attempt passes of the hits {warm['iters'][hits, 1].tolist()}")
     assert expected.sum() >= 25
     for i in range(len(rows)):
-        _assert_oracle(warm, sub, i, f"N={N} window {rows[i]}")
+        assert_exact(warm, i, case["exact"][rows[i]], f"N={N} window {rows[i]}", solved=True)
         if expected[i]:
             assert hits[i], (N, rows[i], warm["iters"][i])
         if not hits[i]:
@@ -159,7 +93,7 @@ def test_shifted_guess_along_the_golden_loop(cuda, golden, N):
 @pytest.mark.parametrize("how", ["nan", "inf", "passes0"])
 def test_unusable_guess_is_the_cold_solve_bit_for_bit(cuda, how):
     N = 10
-    case = _config3_case(N)
+    case = config3_case(N, 16, 5200 + N, margins=True)
     B = len(case["x0"])
     g = case["guesses"].copy()
     odd = np.arange(B) % 2 == 1
@@ -169,11 +103,11 @@ def test_unusable_guess_is_the_cold_solve_bit_for_bit(cuda, how):
         g[odd, 1, 0] = -np.inf  # the first steering angle
     warm, cold = _solve_pair(case, g, passes=0 if how == "passes0" else None)
     unusable = np.ones(B, bool) if how == "passes0" else odd
-    for k in _OUTS:  # iters included
+    for k in OUTS:  # iters included
         np.testing.assert_array_equal(warm[k][unusable], cold[k][unusable], err_msg=k)
     clear = case["margins"] > wn.MARGIN
     for b in np.flatnonzero(~unusable):
-        _assert_oracle(warm, case, b, how)
+        assert_exact(warm, b, case["exact"][b], how, solved=True)
         if clear[b]:
             assert warm["iters"][b, 0] == 0, (how, b, warm["iters"][b])
     assert (~unusable & clear).sum() >= (0 if how == "passes0" else B // 2 - 1)
@@ -187,7 +121,7 @@ def test_poor_guess_never_changes_an_answer(cuda, kind, N):
     optimum, no ADMM) or returns the cold solve's answer."""
     from mpcqp import _lib
 
-    case = _config3_case(N)
+    case = config3_case(N, 16, 5200 + N, margins=True)
     B = len(case["x0"])
     p = case["params"]
     if kind == "zeros":
@@ -203,7 +137,7 @@ def test_poor_guess_never_changes_an_answer(cuda, kind, N):
     print(f"{kind} N={N}: {int(hits.sum())} hits of {B}; warm iters {warm['iters'].tolist()}")
     for b in range(B):
         if hits[b]:
-            _assert_oracle(warm, case, b, f"{kind} N={N}")
+            assert_exact(warm, b, case["exact"][b], f"{kind} N={N}", solved=True)
         else:
             _assert_miss(warm, cold, b, _lib.DEFAULT_GUESS_PASSES, f"{kind} N={N}")
 
@@ -225,8 +159,8 @@ def test_warm_solve_errors_write_nothing(cuda, how):
     N = 40 if how == "n40" else 10
     B = 4
     batch = scenarios.config3(B, horizon=N, seed=9)
-    params = _base(N)
-    ctrl = _controller(params, B, **({"reproducible": 1} if how == "reproducible" else {}))
+    params = base_params(N)
+    ctrl = controller(params, B, **({"reproducible": 1} if how == "reproducible" else {}))
     if how == "after_mixed":
         ctrl.set_classes([params, params])
         ctrl.solve_batch(batch.x0, batch.ref, batch.u_prev, classes=np.zeros(B, np.int32))
@@ -250,68 +184,35 @@ def test_warm_solve_errors_write_nothing(cuda, how):
 def test_guess_may_be_the_output_buffer(cuda):
     """U_guess aliasing U: each wave reads its row before it writes it."""
     N = 10
-    case = _config3_case(N)
+    case = config3_case(N, 16, 5200 + N, margins=True)
     B = len(case["x0"])
-    ctrl = _controller(case["params"], B)
+    ctrl = controller(case["params"], B)
     args = (case["x0"], case["ref"], case["u_prev"])
     first = ctrl.solve_batch(*args)
-    again = _take(ctrl.solve_batch(*args, U_guess=first.U))  # the controller's own U tensor
+    again = take(ctrl.solve_batch(*args, U_guess=first.U))  # the controller's own U tensor
     ctrl.close()
     clear = case["margins"] > wn.MARGIN
     for b in range(B):
-        _assert_oracle(again, case, b, "aliased")
+        assert_exact(again, b, case["exact"][b], "aliased", solved=True)
         if clear[b]:
             assert again["iters"][b, 0] == 0, (b, again["iters"][b])
 
 
 # ---------------------------------------------------------------------- 6. the fleet
-def _tracker(N, V, M, sim_steps, map_resolution=0.8, **kw):
-    from mpcqp.config import MPCConfig
-    from mpcqp.pipeline.fleet import FleetTracker
-
-    mpc = MPCConfig(horizon=N, sim_steps=sim_steps)
-    return FleetTracker(mpc, map_resolution=map_resolution, max_vehicles=V, max_ref_len=M, device="cuda:0",
-                        fused=True, **kw)
-
-
-def _default_plan(golden):
-    g = golden("default_plan.npz")
-    return g, [tuple(map(float, p)) for p in g["path"]]
-
-
-def _varied_fleet(golden, V, seed):
-    g, path = _default_plan(golden)
-    br = golden("branches.npz")
-    off = br["spline_off"]
-    paths = [br["spline"][off[i]:off[i + 1]] for i in range(len(off) - 1)] + [np.asarray(path)]
-    rng = np.random.default_rng(seed)
-    chosen = [paths[i % len(paths)] for i in range(V)]
-    starts = np.array([p[0] for p in chosen]) + rng.uniform(-3, 3, size=(V, 2))
-    return chosen, starts, np.array([p[-1] for p in chosen])
-
-
-def _run(ft, paths, starts, goals, steps=None):
-    ft.reset_from_plans(paths, starts, goals)
-    res = ft.run() if steps is None else (ft.step(steps), ft.result())[1]
-    bufs = {k: ft.buffers()[k].cpu().numpy().copy() for k in _LOOP_BUFFERS}
-    ft.close()
-    return res, bufs
-
-
 @pytest.mark.parametrize("N,steps", [(10, None), (1, 6), (32, 6)])
 def test_warm_loop_without_passes_is_the_cold_loop_bit_for_bit(cuda, golden, N, steps):
     """guess_passes = 0: every solve is cold, every buffer is mpcqp_fleet_loop's (one vehicle per wave)."""
     V = 4
     if N == 10:  # the golden plan, to its goal
-        g, path = _default_plan(golden)
+        g, path = default_plan(golden)
         plans = ([path] * V, np.tile(g["start"], (V, 1)), np.tile(g["goal"], (V, 1)))
         kw = dict(sim_steps=100, map_resolution=float(g["map_resolution"]))
     else:
-        plans = _varied_fleet(golden, V, seed=31 + N)
+        plans = varied_fleet(golden, V, seed=31 + N)[1:]
         kw = dict(sim_steps=steps)
-    _, cold = _run(_tracker(N, V, 128, pairing="off", **kw), *plans, steps=steps)
-    _, warm = _run(_tracker(N, V, 128, warm_start=True, guess_passes=0, **kw), *plans, steps=steps)
-    for k in _LOOP_BUFFERS:
+    _, cold = run_loop(fleet_tracker(N, V, 128, fused=True, pairing="off", **kw), *plans, steps=steps)
+    _, warm = run_loop(fleet_tracker(N, V, 128, fused=True, warm_start=True, guess_passes=0, **kw), *plans, steps=steps)
+    for k in LOOP_BUFFERS_MASK:
         np.testing.assert_array_equal(warm[k], cold[k], err_msg=k)
     assert (cold["steps"][:V] > 0).all()
 
@@ -322,13 +223,13 @@ def test_warm_loop_reproduces_the_reference_closed_loop(cuda, golden, N, sim_ste
     loop (closed_loop.npz) within the cold loop's tolerances, and the cold fused loop itself closely."""
     from mpcqp import _lib
 
-    g, path = _default_plan(golden)
+    g, path = default_plan(golden)
     loop = golden("closed_loop.npz")
     V = 4
     plans = ([path] * V, np.tile(g["start"], (V, 1)), np.tile(g["goal"], (V, 1)))
     kw = dict(sim_steps=sim_steps, map_resolution=float(g["map_resolution"]))
-    rc, cold = _run(_tracker(N, V, 64, pairing="off", **kw), *plans)
-    rw, warm = _run(_tracker(N, V, 64, warm_start=True, **kw), *plans)
+    rc, cold = run_loop(fleet_tracker(N, V, 64, fused=True, pairing="off", **kw), *plans)
+    rw, warm = run_loop(fleet_tracker(N, V, 64, fused=True, warm_start=True, **kw), *plans)
     ref_states = loop[f"N{N}_states"]
     assert (rw.phase == _lib.FLEET_GOAL).all() and (rw.steps == len(ref_states)).all()
     for v in range(V):
@@ -347,14 +248,14 @@ def test_warm_loop_relaxation_branches(cuda, golden):
     from mpcqp import _lib
 
     N, steps, V = 10, 20, 6
-    g, path = _default_plan(golden)
+    g, path = default_plan(golden)
     out = []
     for kw in (dict(pairing="off"), dict(warm_start=True)):
-        ft = _tracker(N, V, 64, steps, float(g["map_resolution"]), **kw)
+        ft = fleet_tracker(N, V, 64, steps, float(g["map_resolution"]), fused=True, **kw)
         ft.reset_from_plans([path] * V, np.tile(g["start"], (V, 1)), np.tile(g["goal"], (V, 1)))
         ft.buffers()["state"][2, 0] = float("nan")
         res = ft.run()
-        out.append((res, {k: ft.buffers()[k].cpu().numpy().copy() for k in ("mask", "status", "phase", "steps")}))
+        out.append((res, loop_buffers(ft, ("mask", "status", "phase", "steps"))))
         ft.close()
     (rc, cold), (rw, warm) = out
     for k in ("mask", "status", "phase", "steps"):
@@ -380,22 +281,22 @@ def test_warm_loop_longest_first_dispatch_order(cuda, golden):
 
     N, steps = 3, 4
     V = 8 * torch.cuda.get_device_properties(0).multi_processor_count + 5
-    paths, starts, goals = _varied_fleet(golden, V, seed=6)
+    _, paths, starts, goals = varied_fleet(golden, V, seed=6)
     s0 = initial_states(paths, starts)
     out, refs = [], None
     for kw in ({}, dict(warm_start=True, guess_passes=0), dict(warm_start=True)):
-        ft = _tracker(N, V, 128, steps, **kw)
-        if refs is None:  # _varied_fleet cycles through 13 plans: one reference per plan, built once
+        ft = fleet_tracker(N, V, 128, steps, fused=True, **kw)
+        if refs is None:  # varied_fleet cycles through 13 plans: one reference per plan, built once
             distinct = [build_reference(paths[i], ft.mpc.v_px_s, N, ft.mpc.dt) for i in range(13)]
             assert all(paths[v] is paths[v - 13] for v in range(13, 26))
             refs = [distinct[v % 13] for v in range(V)]
         ft.reset(refs, s0, goals)
         ft.run()
-        out.append({k: ft.buffers()[k].cpu().numpy().copy() for k in _LOOP_BUFFERS})
+        out.append(loop_buffers(ft, LOOP_BUFFERS_MASK))
         ft.close()
     plain, cold, warm = out
     assert (plain["steps"] == steps).any()
-    for k in _LOOP_BUFFERS:
+    for k in LOOP_BUFFERS_MASK:
         np.testing.assert_array_equal(cold[k], plain[k], err_msg=k)
     for k in ("phase", "steps", "path_idx"):
         np.testing.assert_array_equal(warm[k], plain[k], err_msg=k)

@@ -15,64 +15,22 @@ and sums its line search in tree order.  Checks:
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 import pytest
+from gpu_helpers import OUTS, REL_TOL, base_params, check_against_oracle, rel, solve_with_model
 
 pytestmark = pytest.mark.gpu
-
-REL_TOL = 1e-8
-
-
-def _params(N):
-    from mpcqp.config import MPCConfig
-
-    return MPCConfig(horizon=N).to_parameters(0.8)
-
-
-def _rel(a, b):
-    return float(np.abs(a - b).max() / max(1.0, np.abs(b).max()))
-
-
-def _solve_with_model(params, x0, ref, u_prev, **settings):
-    import torch
-    from mpcqp import _lib
-    from mpcqp.control.mpc_controller import BatchedMPCController
-
-    N = int(params.horizon)
-    B = len(x0)
-    ctrl = BatchedMPCController(params, B, device="cuda:0", **settings)
-    sol = ctrl.solve_batch(x0, ref, u_prev)
-    torch.cuda.synchronize()
-    out = {k: getattr(sol, k).cpu().numpy().copy() for k in sol._fields}
-    L = _lib.lib()
-    ptr = L.mpcqp_model_buffer(ctrl._ws)
-    model = None  # the fused one-wave solve builds its model on chip: no model buffer
-    if ptr:
-        model = np.zeros((B, L.mpcqp_model_stride(N)))
-        hip = ctypes.CDLL("libamdhip64.so")
-        hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-        assert hip.hipMemcpy(model.ctypes.data, ptr, model.nbytes, 2) == 0
-    ctrl.close()
-    return out, model
 
 
 @pytest.mark.parametrize("N", [32, 40, 48, 63, 64, 80, 127])
 def test_long_horizons_match_exact_oracle(cuda, N):
-    import mpc_oracle as mo
     from mpcqp import scenarios
 
     batch = scenarios.config3(24 if N < 64 else 8, horizon=N, seed=300 + N)
-    params = _params(N)
-    out, _ = _solve_with_model(params, batch.x0, batch.ref, batch.u_prev)
+    params = base_params(N)
+    out, _ = solve_with_model(params, batch.x0, batch.ref, batch.u_prev)
     assert (out["status"] == 1).all(), np.unique(out["status"], return_counts=True)
-    for b in range(batch.size):
-        ex = mo.solve_exact(params, batch.x0[b], batch.ref[b], batch.u_prev[b])
-        assert ex.converged
-        e = max(_rel(out["U"][b], ex.Umat), _rel(out["X"][b], ex.X), _rel(out["u0"][b], ex.Umat[:, 0]))
-        assert e <= REL_TOL, f"N={N} QP {b}: rel err {e:.3e}"
-        assert np.array_equal(out["active"][b], ex.active), f"N={N} QP {b}: active set differs"
+    check_against_oracle(params, batch.x0, batch.ref, batch.u_prev, out, range(batch.size), f"N={N}")
 
 
 @pytest.mark.parametrize("N,settings", [(32, {}), (40, {}), (40, {"polish_near": 0.0}),
@@ -85,8 +43,8 @@ def test_long_horizons_bit_exact_with_c_restatement(cuda, N, settings):
     from mpcqp import scenarios
 
     batch = scenarios.config3(48 if N < 64 else 16, horizon=N, seed=700 + N)
-    params = _params(N)
-    out, model = _solve_with_model(params, batch.x0, batch.ref, batch.u_prev, reproducible=1, **settings)
+    params = base_params(N)
+    out, model = solve_with_model(params, batch.x0, batch.ref, batch.u_prev, reproducible=1, **settings)
     ref = cpu_solver.cpu_solve_models(params, model, **settings)
     assert np.array_equal(out["status"], ref["status"])
     assert np.array_equal(out["iters"], ref["iters"]), np.argwhere((out["iters"] != ref["iters"]).any(axis=1))
@@ -107,14 +65,14 @@ def test_long_horizons_fast_mode_against_c_restatement(cuda, N, settings):
     from mpcqp import scenarios
 
     batch = scenarios.config3(64, horizon=N, seed=900 + N)
-    params = _params(N)
-    out, model = _solve_with_model(params, batch.x0, batch.ref, batch.u_prev, **settings)
+    params = base_params(N)
+    out, model = solve_with_model(params, batch.x0, batch.ref, batch.u_prev, **settings)
     # N = 32 runs the one-wave kernel with K1 fused (no model buffer): the C code from the inputs
     ref = (cpu_solver.cpu_solve_models(params, model, **settings) if model is not None else
            cpu_solver.cpu_solve(params, batch.x0, batch.ref, batch.u_prev, **settings))
     assert np.array_equal(out["status"], ref["status"])
     assert np.array_equal(out["active"], ref["active"])
-    assert _rel(out["U"], ref["U"]) <= REL_TOL and _rel(out["X"], ref["X"]) <= REL_TOL
+    assert rel(out["U"], ref["U"]) <= REL_TOL and rel(out["X"], ref["X"]) <= REL_TOL
     same = (out["iters"] == ref["iters"]).all(axis=1)
     assert same.all(), f"QPs {np.flatnonzero(~same)[:10]} disagree on iteration counts"
 
@@ -127,10 +85,10 @@ def test_mid_kernel_deterministic_below_the_bucket(cuda, N):
     from mpcqp import scenarios
 
     batch = scenarios.config3(256, horizon=N, seed=1300 + N)
-    params = _params(N)
-    a, _ = _solve_with_model(params, batch.x0, batch.ref, batch.u_prev)
-    b, _ = _solve_with_model(params, batch.x0, batch.ref, batch.u_prev)
-    for k in ("U", "X", "u0", "status", "iters", "active"):
+    params = base_params(N)
+    a, _ = solve_with_model(params, batch.x0, batch.ref, batch.u_prev)
+    b, _ = solve_with_model(params, batch.x0, batch.ref, batch.u_prev)
+    for k in OUTS:
         assert np.array_equal(a[k].view(np.uint8), b[k].view(np.uint8)), f"N={N}: {k} differs between runs"
 
 
@@ -146,16 +104,16 @@ def test_reproducible_mode_bit_exact_with_c_restatement(cuda, N, config, setting
     from mpcqp import scenarios
 
     batch = scenarios.config2(64, horizon=N) if config == "config2" else scenarios.config3(64, horizon=N, seed=800 + N)
-    params = _params(N)
-    out, model = _solve_with_model(params, batch.x0, batch.ref, batch.u_prev, reproducible=1, **settings)
+    params = base_params(N)
+    out, model = solve_with_model(params, batch.x0, batch.ref, batch.u_prev, reproducible=1, **settings)
     ref = cpu_solver.cpu_solve_models(params, model, **settings)
     assert np.array_equal(out["status"], ref["status"])
     assert np.array_equal(out["iters"], ref["iters"]), np.argwhere((out["iters"] != ref["iters"]).any(axis=1))
     assert np.array_equal(out["U"], ref["U"])
     assert np.array_equal(out["X"], ref["X"])
     assert np.array_equal(out["active"], ref["active"])
-    fast, _ = _solve_with_model(params, batch.x0, batch.ref, batch.u_prev, **settings)
-    assert np.array_equal(fast["active"], out["active"]) and _rel(fast["U"], out["U"]) <= REL_TOL
+    fast, _ = solve_with_model(params, batch.x0, batch.ref, batch.u_prev, **settings)
+    assert np.array_equal(fast["active"], out["active"]) and rel(fast["U"], out["U"]) <= REL_TOL
 
 
 @pytest.mark.parametrize("N", [63, 64, 100, 127])
@@ -170,14 +128,14 @@ def test_long_window_k1_matches_restatement(cuda, N):
     ref[::3, 30:, 2] += 2 * np.pi
     ref[1::3, 64:, 2] -= 4 * np.pi
     ref[2::3, 65:, 2] += 2 * np.pi
-    params = _params(N)
-    out, model = _solve_with_model(params, batch.x0, ref, batch.u_prev, reproducible=1)
+    params = base_params(N)
+    out, model = solve_with_model(params, batch.x0, ref, batch.u_prev, reproducible=1)
     cpu = cpu_solver.cpu_solve(params, batch.x0, ref, batch.u_prev, want_model=True)["model"]
     # window rows (x, y, unwrapped yaw, v), x0 and u_prev bit for bit; the linearisation's
     # coefficients to 1e-12 (device sincos vs the host libm)
     assert np.array_equal(model[:, 7 * N: 11 * N + 10], cpu[:, 7 * N: 11 * N + 10])
     assert np.array_equal(model[:, 7 * N + 2: 11 * N + 4: 4], np.unwrap(ref[:, :, 2], axis=1))
-    assert _rel(model[:, : 7 * N], cpu[:, : 7 * N]) <= 1e-12
+    assert rel(model[:, : 7 * N], cpu[:, : 7 * N]) <= 1e-12
 
 
 def test_horizon_past_the_thread_count(cuda):
@@ -189,12 +147,12 @@ def test_horizon_past_the_thread_count(cuda):
 
     N = 200
     batch = scenarios.config3(2, horizon=N, seed=5)
-    params = _params(N)
+    params = base_params(N)
     for b in range(batch.size):
         u0, X, U = MPCController(params).solve(batch.x0[b], batch.ref[b], u_prev=batch.u_prev[b])
         ex = mo.solve_exact(params, batch.x0[b], batch.ref[b], batch.u_prev[b])
         assert ex.converged and U is not None
-        assert max(_rel(U, ex.Umat), _rel(X, ex.X)) <= REL_TOL
+        assert max(rel(U, ex.Umat), rel(X, ex.X)) <= REL_TOL
 
 
 def test_long_horizon_newton_and_max_iter(cuda):
@@ -204,35 +162,34 @@ def test_long_horizon_newton_and_max_iter(cuda):
 
     N = 36
     batch = scenarios.config3(32, horizon=N, seed=9)
-    params = _params(N)
+    params = base_params(N)
     for method, settings in (("newton", {}), ("admm", dict(max_iter=40, polish_from=0, polish_near=0.0))):
-        out, model = _solve_with_model(params, batch.x0, batch.ref, batch.u_prev, method=method, reproducible=1,
+        out, model = solve_with_model(params, batch.x0, batch.ref, batch.u_prev, method=method, reproducible=1,
                                        **settings)
         ref = cpu_solver.cpu_solve_models(params, model, method=1 if method == "newton" else 0, **settings)
         assert np.array_equal(out["status"], ref["status"]), method
         assert np.array_equal(out["iters"], ref["iters"]), method
         assert np.array_equal(out["U"], ref["U"]), method
-        fast, _ = _solve_with_model(params, batch.x0, batch.ref, batch.u_prev, method=method, **settings)
+        fast, _ = solve_with_model(params, batch.x0, batch.ref, batch.u_prev, method=method, **settings)
         assert np.array_equal(fast["status"], ref["status"]), method
-        assert _rel(fast["U"], ref["U"]) <= REL_TOL, method
+        assert rel(fast["U"], ref["U"]) <= REL_TOL, method
 
 
 def test_mpc_controller_drop_in_at_horizon_40(cuda):
     """MPCController(params).solve at a horizon the one-wave kernel cannot hold, with a window
     longer than N+1 rows (the reference reads rows 0..N)."""
     import mpc_oracle as mo
-    from mpcqp.config import MPCConfig
     from mpcqp.control.mpc_controller import MPCController
     from mpcqp import scenarios
     from mpcqp.control.ref_builder import build_reference
 
     plan = scenarios.load_default_plan()
     ref_g = build_reference(plan["path"], 15.0, 40, 0.1)
-    params = MPCConfig(horizon=40).to_parameters(0.8)
+    params = base_params(40)
     x0 = np.array([plan["start"][0], plan["start"][1], float(plan["yaw0"]), 5.0])
     u0, X, U = MPCController(params).solve(x0, ref_g[:45], u_prev=np.zeros(2))
     ex = mo.solve_exact(params, x0, ref_g[:41], np.zeros(2))
-    assert _rel(U, ex.Umat) <= REL_TOL and _rel(X, ex.X) <= REL_TOL
+    assert rel(U, ex.Umat) <= REL_TOL and rel(X, ex.X) <= REL_TOL
     assert X.shape == (4, 41) and U.shape == (2, 40)
 
 

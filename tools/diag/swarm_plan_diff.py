@@ -17,20 +17,20 @@ def main():
     V = int(sys.argv[1]) if len(sys.argv) > 1 else 100
     pair_seed = int(sys.argv[2]) if len(sys.argv) > 2 else 7
     import rrt_oracle as ro
-    from test_gpu_swarm import _oracle_plan, _pairs, _planner_params
+    from gpu_helpers import oracle_plan, pairs, planner_params
 
     from mpcqp.planning.rrt_star import BatchedRRTStarPlanner, draw_samples
 
     occ = np.load(ROOT / "tests" / "golden" / "default_plan.npz")["occupancy"]
-    starts, goals = _pairs(occ, V, pair_seed)
-    prm = _planner_params()
+    starts, goals = pairs(occ, V, pair_seed)
+    prm = planner_params()
     pl = BatchedRRTStarPlanner(occ, prm, device="cuda:0")
     nodes, count, meta = pl.grow(starts, goals, np.arange(V))
     nodes, count, meta = nodes.cpu().numpy(), count.cpu().numpy(), meta.cpu().numpy()
     final = pl.paths_batch(starts, goals, np.arange(V), smoothing="device")
     report = []
     for v in range(V):
-        p = _planner_params(v)
+        p = planner_params(v)
         smp = draw_samples(v, goals[v], occ.shape, p.goal_sample_rate, p.max_iterations)
         on, oit, ogi = ro.grow_tree(occ, starts[v], goals[v], smp, step=p.step, goal_radius=p.goal_radius,
                                     rewire_radius=p.rewire_radius, collision_step=p.collision_step)
@@ -48,7 +48,7 @@ def main():
                 cd = on[pd, 2] + np.hypot(*(on[pd, :2] - on[k, :2])) if pd >= 0 else None
                 co = on[po, 2] + np.hypot(*(on[po, :2] - on[k, :2])) if po >= 0 else None
                 row.setdefault("ties", []).append([int(k), pd, po, cd, co])
-        op = _oracle_plan(occ, starts[v], goals[v], v)
+        op = oracle_plan(occ, starts[v], goals[v], v)
         fp = final[v]
         if op is None or fp is None:
             row["plan"] = [op is None, fp is None]

@@ -1,13 +1,14 @@
 """Development: per-phase cycles of the long-horizon kernel (tools/diag/libmpcqp_wstamps.so,
 -DMPCQP_WIDE_STAMPS): python tools/diag/wide_stamps.py [N] [B]"""
-import ctypes, json, os, sys
+import json, os, sys
 from pathlib import Path
 ROOT = Path(__file__).resolve().parents[2]
 os.environ.setdefault("MPCQP_LIB", str(ROOT / "tools" / "diag" / "libmpcqp_wstamps.so"))
 os.environ.setdefault("MPCQP_ABI_ANY", "1")
-sys.path.insert(0, str(ROOT / "rrt-mpc_amd"))
+sys.path[:0] = [str(ROOT / "rrt-mpc_amd"), str(ROOT / "oracle"), str(ROOT / "tests")]
 import numpy as np
 import torch
+from gpu_helpers import d2h
 from mpcqp import _lib, scenarios
 from mpcqp.config import MPCConfig
 from mpcqp.control.mpc_controller import BatchedMPCController
@@ -19,10 +20,7 @@ ctrl.solve_batch(b.x0, b.ref, b.u_prev)
 torch.cuda.synchronize()
 L = _lib.lib()
 SS = L.mpcqp_state_stride(N)
-st = np.zeros((B, SS))
-hip = ctypes.CDLL("libamdhip64.so")
-hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-assert hip.hipMemcpy(st.ctypes.data, L.mpcqp_state_buffer(ctrl._ws), st.nbytes, 2) == 0
+st = d2h(L.mpcqp_state_buffer(ctrl._ws), np.zeros((B, SS)))
 n = 2 * N
 off = n * (n + 1)
 names = ["setup", "admm.factor", "admm.iteration", "admm.check", "polish.form", "polish.sweep", "polish.solve",
