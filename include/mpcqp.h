@@ -205,10 +205,13 @@ int mpcqp_solve(mpcqp_ws* ws, int B, double* u0, double* X, double* U, int32_t* 
  * equal cold ones to rounding, not bit for bit.
  * Solves the last plain mpcqp_build of the same B: MPCQP_E_STATE without one, and after
  * mpcqp_build_mixed.  NULL U_guess or status: MPCQP_E_ARG.  The fused one-wave kernel only (N <= 32,
- * fast mode, no debug_state; one QP per wave whatever mpcqp_set_pairing says): other parameter blocks
- * return MPCQP_E_HORIZON.  In every error case nothing is enqueued and nothing is written.  U_guess must
- * stay valid until the solve has run (stream order); it may be the U output itself (each wave reads
- * its row before it writes it).
+ * fast mode, no debug_state): other parameter blocks return MPCQP_E_HORIZON.  In every error case
+ * nothing is enqueued and nothing is written.  U_guess must stay valid until the solve has run (stream
+ * order); it may be the U output itself (each wave, or half of one, reads its row before it writes it).
+ * Pairing (mpcqp_set_pairing): MPCQP_PAIR_ON runs two QPs per wave where the paired kernel exists
+ * (N <= 15), each half of a wave through its own attempt -- one may hit while the other misses -- with
+ * every output, iters included, equal to the one-QP-per-wave launch bit for bit; MPCQP_PAIR_OFF never
+ * pairs; MPCQP_PAIR_AUTO keeps one QP per wave for warm launches, whatever the batch size.
  */
 int mpcqp_solve_warm(mpcqp_ws* ws, int B, const double* U_guess, int guess_passes, double* u0, double* X, double* U,
                      int32_t* status, int32_t* iters, uint8_t* active, void* stream);
@@ -279,7 +282,9 @@ int mpcqp_solve_served_warm(mpcqp_ws* ws, int guess_passes);
  * padding): lanes 0-31 and 32-63 of a wave solve two QPs of the batch (mpcqp_solve with the model
  * built in the solve) or two vehicles of the fused loop (mpcqp_fleet_loop, mpcqp_swarm_loop), with
  * the results of the one-QP-per-wave kernel bit for bit.  MPCQP_PAIR_AUTO (the default) pairs once
- * a launch has more QPs than the device has wave slots (8 per CU); ON / OFF force it.  Ignored where
+ * a launch has more QPs than the device has wave slots (8 per CU); ON / OFF force it.  The warm calls
+ * (mpcqp_solve_warm, mpcqp_fleet_loop_warm, mpcqp_fleet_loop_warm_carry) pair under ON only: AUTO
+ * leaves them at one per wave.  Ignored where
  * the one-wave kernel does not run (N > 15, reproducible, debug_state).  No counterpart in the
  * reference (OSQP solves one QP per call). */
 #define MPCQP_PAIR_OFF 0
@@ -415,10 +420,51 @@ int mpcqp_fleet_loop_mixed(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fle
  * Argument checks, the device's validation of the loop state, the exits, the longest-first dispatch and
  * the invalidation of both workspaces' builds are mpcqp_fleet_loop's.  The fused loop only -- N <= 32 in
  * fast mode without debug_state; other parameter blocks return MPCQP_E_HORIZON, and then nothing is
- * enqueued and nothing invalidated.  One vehicle per wave whatever mpcqp_set_pairing says; the replan
- * trigger is off.  Out of scope: the stepped fleet, mixed classes and the swarm. */
+ * enqueued and nothing invalidated.  The replan trigger is off.  Out of scope: the stepped fleet, mixed
+ * classes and the swarm.
+ * Pairing (mpcqp_set_pairing on `nominal`): MPCQP_PAIR_ON runs two vehicles per wave where the paired
+ * kernel exists (N <= 15), dispatched as the paired mpcqp_fleet_loop, every buffer equal to the
+ * one-vehicle-per-wave warm loop's bit for bit (with guess_passes <= 0: to the paired mpcqp_fleet_loop's);
+ * MPCQP_PAIR_OFF never pairs; MPCQP_PAIR_AUTO keeps one vehicle per wave for warm launches, whatever the
+ * fleet's size. */
 int mpcqp_fleet_loop_warm(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, int steps, int guess_passes,
                           void* stream);
+
+/* mpcqp_fleet_loop_warm with the guess carried across launches (additive to ABI 9), for a caller who
+ * looks at the fleet every few steps:
+ *   U_carry  V x 2 x N doubles (device), in/out, the layout of U; valid until the launch has run
+ * A RUNNING vehicle's first step starts from its row (shifted one step down like every later one) instead
+ * of cold, and after its last step of the launch the U of its last accepted solve is stored there,
+ * unshifted.  A row with any non-finite entry is an unusable guess: that first step is cold, and with a
+ * NaN-filled U_carry every buffer equals mpcqp_fleet_loop_warm's bit for bit.  A run split into launches
+ * of any sizes over one carried buffer equals the same run in one mpcqp_fleet_loop_warm launch bit for
+ * bit, under the same pairing.  With guess_passes <= 0 the buffers are mpcqp_fleet_loop's bit for bit,
+ * and the rows are still written.  Rows of vehicles that are not RUNNING, or that accepted no solve in
+ * the launch (an abort or an exit at their first step), are left as they were.
+ * NULL U_carry: MPCQP_E_ARG.  Parameter blocks without the fused one-wave loop (N > 32, reproducible,
+ * debug_state): MPCQP_E_HORIZON.  In both cases nothing is enqueued and nothing invalidated.  Pairing
+ * follows mpcqp_fleet_loop_warm's rule (ON pairs at N <= 15, OFF never, MPCQP_PAIR_AUTO keeps one vehicle
+ * per wave).  Everything else is mpcqp_fleet_loop_warm's: argument checks, the device's validation of the
+ * loop state, the exits, the dispatch order, the invalidation of both workspaces' builds. */
+int mpcqp_fleet_loop_warm_carry(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, int steps,
+                                int guess_passes, double* U_carry, void* stream);
+
+/* What the last solver launch recorded on this workspace did (additive to ABI 9; host bookkeeping, no
+ * device call): info = {kind (MPCQP_LAUNCH_*), QPs or vehicles per wave (1 or 2), workgroups launched,
+ * B or V}.  Recorded by mpcqp_solve (plain and mixed builds), mpcqp_solve_warm and the fused-loop calls
+ * (mpcqp_fleet_loop, _mixed, _warm, _warm_carry: on `nominal`; mpcqp_swarm_loop's launches record as
+ * MPCQP_LAUNCH_LOOP); a call that returns an error or enqueues nothing (B, V or steps 0), and the stepped
+ * fleet and swarm, record nothing.  {MPCQP_LAUNCH_NONE, 0, 0, 0} before any launch and after
+ * mpcqp_set_params.  NULL ws or info: MPCQP_E_ARG. */
+#define MPCQP_LAUNCH_NONE 0
+#define MPCQP_LAUNCH_SOLVE 1
+#define MPCQP_LAUNCH_SOLVE_MIXED 2
+#define MPCQP_LAUNCH_SOLVE_WARM 3
+#define MPCQP_LAUNCH_LOOP 4
+#define MPCQP_LAUNCH_LOOP_MIXED 5
+#define MPCQP_LAUNCH_LOOP_WARM 6
+#define MPCQP_LAUNCH_LOOP_WARM_CARRY 7
+int mpcqp_launch_info(const mpcqp_ws* ws, int32_t info[4]);
 
 /*
  * Batched build_reference: src/control/ref_builder.py:10-22 with

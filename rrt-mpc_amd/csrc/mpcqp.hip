@@ -208,6 +208,10 @@ bool use_pairs(const mpcqp_ws* ws, int count) {
   // own, and pairing would only make each wave wait for the slower of its two QPs
   return ws->cus > 0 && count > 8 * ws->cus;
 }
+bool use_pairs_warm(const mpcqp_ws* ws) {
+  const HorizonKernels* k = one_wave(ws->p);
+  return ws->pairing == MPCQP_PAIR_ON && k && k->pair_warm;
+}
 }  // namespace mpcqp
 
 extern "C" {
@@ -265,6 +269,7 @@ int mpcqp_set_params(mpcqp_ws* ws, const mpcqp_params* p) {
   // from the params in effect at solve time, the K1 kernel from those at build time): new params
   // invalidate it, and the next mpcqp_solve needs a new mpcqp_build.
   ws->invalidate();
+  ws->no_launch();
   return MPCQP_OK;
 }
 
@@ -379,6 +384,12 @@ int mpcqp_build_mixed(mpcqp_ws* ws, int B, const double* x0, const double* ref, 
   return build(ws, B, x0, ref, u_prev, cls, stream);
 }
 
+// a solve launch's return code, recorded for mpcqp_launch_info where the launch went out
+static int recorded(mpcqp_ws* ws, int rc, int kind, int per_wave, int B) {
+  if (rc == MPCQP_OK) ws->launched_as(kind, per_wave, B);
+  return rc;
+}
+
 int mpcqp_solve(mpcqp_ws* ws, int B, double* u0, double* X, double* U, int32_t* status, int32_t* iters,
                 uint8_t* active, void* stream) {
   if (!ws || !status) return fail(MPCQP_E_ARG, "null argument");
@@ -398,10 +409,11 @@ int mpcqp_solve(mpcqp_ws* ws, int B, double* u0, double* X, double* U, int32_t* 
     L.K = ws->n_classes;
     // the workgroup-per-QP launchers read L.cls themselves; the one-wave kernel has an entry of its own
     (k ? k->mixed : mpcqp::launcher(ws->p))(s, L);
-    return mpcqp::launched("k_solve_mixed");
+    return recorded(ws, mpcqp::launched("k_solve_mixed"), MPCQP_LAUNCH_SOLVE_MIXED, 1, B);
   }
-  (L.ref && mpcqp::use_pairs(ws, B) ? k->pair : mpcqp::launcher(ws->p))(s, L);  // use_pairs: one wave, k->pair set
-  return mpcqp::launched("k_solve");
+  const bool pair = L.ref && mpcqp::use_pairs(ws, B);  // use_pairs: one wave, k->pair set
+  (pair ? k->pair : mpcqp::launcher(ws->p))(s, L);
+  return recorded(ws, mpcqp::launched("k_solve"), MPCQP_LAUNCH_SOLVE, pair ? 2 : 1, B);
 }
 
 int mpcqp_solve_warm(mpcqp_ws* ws, int B, const double* U_guess, int guess_passes, double* u0, double* X, double* U,
@@ -423,8 +435,16 @@ int mpcqp_solve_warm(mpcqp_ws* ws, int B, const double* U_guess, int guess_passe
   L.u_prev = built.u_prev;
   L.guess = U_guess;
   L.guess_passes = guess_passes;
-  k->warm(static_cast<hipStream_t>(stream), L);
-  return mpcqp::launched("k_solve_warm");
+  const bool pair = mpcqp::use_pairs_warm(ws);  // MPCQP_PAIR_ON and N <= 15 only: AUTO keeps one QP per wave
+  (pair ? k->pair_warm : k->warm)(static_cast<hipStream_t>(stream), L);
+  return recorded(ws, mpcqp::launched(pair ? "k_solve_pair_warm" : "k_solve_warm"), MPCQP_LAUNCH_SOLVE_WARM,
+                  pair ? 2 : 1, B);
+}
+
+int mpcqp_launch_info(const mpcqp_ws* ws, int32_t info[4]) {
+  if (!ws || !info) return fail(MPCQP_E_ARG, "null argument");
+  for (int i = 0; i < 4; ++i) info[i] = ws->last_launch[i];
+  return MPCQP_OK;
 }
 
 // ------------------------------------------------------------------ B = 1 path

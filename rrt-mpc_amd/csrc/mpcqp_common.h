@@ -584,6 +584,7 @@ struct LoopLaunch {
   const int32_t* cls = nullptr;  // a class per vehicle (V indices) into the K classes
   int K = 0;
   int guess_passes = 0;  // the warm loop's pass limit per attempt
+  double* carry = nullptr;  // k_fleet_loop_warm_carry: the carried guess, V x 2 x N (nullable)
 };
 typedef void (*fleet_loop_t)(hipStream_t, const LoopLaunch&);
 // The kernels of one horizon of the one-wave family (N < MPCQP_WIDE_MIN_HORIZON; the launch_*<N>
@@ -591,9 +592,11 @@ typedef void (*fleet_loop_t)(hipStream_t, const LoopLaunch&);
 // QPs per wave, fused K1; nullptr above kPairMaxHorizon), k_serve (the B = 1 server), k_fleet_loop
 // (the fused closed loop), k_fleet_loop_mixed (the same with a class per vehicle), k_solve_warm (from a
 // caller's guess), k_fleet_loop_warm (the fused loop, each step from the one before) and k_serve_warm
-// (the B = 1 server from a caller's guess).  The object that instantiates a horizon registers it from
-// a namespace-scope initialiser (register_horizons, mpcqp_solve.h); an all-null entry is a horizon not
-// compiled in.
+// (the B = 1 server from a caller's guess), k_solve_pair_warm (two QPs per wave from a caller's guess;
+// nullptr above kPairMaxHorizon) and k_fleet_loop_warm_carry (the warm loop with the guess carried across
+// launches; its launcher runs two vehicles per wave where tr.pair).  The object that instantiates a
+// horizon registers it from a namespace-scope initialiser (register_horizons, mpcqp_solve.h); an
+// all-null entry is a horizon not compiled in.
 struct HorizonKernels {
   launcher_t solve, mixed, pair;
   serve_t serve;
@@ -601,6 +604,8 @@ struct HorizonKernels {
   launcher_t warm;
   fleet_loop_t loop_warm;
   serve_warm_t serve_warm;
+  launcher_t pair_warm;
+  fleet_loop_t loop_warm_carry;
 };
 // fills entry N of the table in mpcqp.hip (constant-initialised, so the order of the objects'
 // initialisers does not matter)
@@ -742,6 +747,16 @@ struct mpcqp_ws {
   // dloop_cap classes, filled from the two class tables by a kernel on the launch stream at every call
   mpcqp_params* dloop_classes = nullptr;
   int dloop_cap = 0;
+  // mpcqp_launch_info: the last solver launch recorded here {MPCQP_LAUNCH_*, QPs (vehicles) per wave,
+  // workgroups, B or V}; host bookkeeping, written by launched_as() and cleared by mpcqp_set_params
+  int32_t last_launch[4] = {MPCQP_LAUNCH_NONE, 0, 0, 0};
+  void launched_as(int kind, int per_wave, int count) {
+    last_launch[0] = kind;
+    last_launch[1] = per_wave;
+    last_launch[2] = (count + per_wave - 1) / per_wave;
+    last_launch[3] = count;
+  }
+  void no_launch() { last_launch[0] = last_launch[1] = last_launch[2] = last_launch[3] = 0; }
 };
 
 namespace mpcqp {
@@ -751,10 +766,15 @@ namespace mpcqp {
 // checks -- both builds invalidated, the parameter blocks stored on the stream (L.cls: the two class
 // tables, else the workspaces' own blocks; L.P is set here), the longest-first dispatch order when the
 // vehicles outnumber the wave slots (L.tr.order is set here), pairing under use_pairs where may_pair
-// (the plain loop), the launch, and `name` in its launch error.
+// (the plain loop; the warm loops hand in L.tr.pair themselves), the launch, its record on `nominal` as
+// `kind` (MPCQP_LAUNCH_*, mpcqp_launch_info), and `name` in its launch error.
 fleet_loop_t fused_loop(const mpcqp_ws* nominal, const mpcqp_ws* relaxed, fleet_loop_t HorizonKernels::*which);
-int enqueue_fused_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, fleet_loop_t loop, const char* name, bool may_pair,
-                       LoopLaunch L, hipStream_t s);
+int enqueue_fused_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, fleet_loop_t loop, const char* name, int kind,
+                       bool may_pair, LoopLaunch L, hipStream_t s);
+// two QPs (vehicles) per wave for a warm launch (mpcqp_solve_warm, mpcqp_fleet_loop_warm[_carry])?  Only
+// under MPCQP_PAIR_ON and where the paired kernels exist: MPCQP_PAIR_AUTO keeps warm launches at one per
+// wave.  Defined in mpcqp.hip.
+bool use_pairs_warm(const mpcqp_ws* ws);
 // allocate ws->model / ws->state (max_batch QPs) if requested and not yet there; refuses to allocate
 // on a capturing stream (the first use must run outside a capture); defined in mpcqp.hip
 int ensure_buffers(mpcqp_ws* ws, bool model, bool state, hipStream_t s);

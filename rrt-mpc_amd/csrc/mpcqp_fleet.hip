@@ -275,8 +275,8 @@ fleet_loop_t fused_loop(const mpcqp_ws* nominal, const mpcqp_ws* relaxed, fleet_
   return kn && kr && kn->*which == kr->*which ? kn->*which : nullptr;
 }
 
-int enqueue_fused_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, fleet_loop_t loop, const char* name, bool may_pair,
-                       LoopLaunch L, hipStream_t s) {
+int enqueue_fused_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, fleet_loop_t loop, const char* name, int kind,
+                       bool may_pair, LoopLaunch L, hipStream_t s) {
   nominal->invalidate();  // as mpcqp_fleet_step: a later mpcqp_solve needs its own build
   relaxed->invalidate();
   if (L.cls) {
@@ -293,9 +293,11 @@ int enqueue_fused_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, fleet_loop_t loop, 
     hipLaunchKernelGGL(k_fleet_order, dim3(1), dim3(kOrderBuckets), 0, s, *L.f, nominal->dorder);
     L.tr.order = nominal->dorder;
   }
-  L.tr.pair = may_pair && use_pairs(nominal, L.f->vehicles);
+  if (may_pair) L.tr.pair = use_pairs(nominal, L.f->vehicles);
   loop(s, L);
-  return launched(name);
+  const int rc = launched(name);
+  if (rc == MPCQP_OK) nominal->launched_as(kind, L.tr.pair ? 2 : 1, L.f->vehicles);
+  return rc;
 }
 }  // namespace mpcqp
 
@@ -309,7 +311,8 @@ int mpcqp_fleet_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f,
   hipStream_t s = static_cast<hipStream_t>(stream);
   const mpcqp::fleet_loop_t loop = mpcqp::fused_loop(nominal, relaxed, &mpcqp::HorizonKernels::loop);
   if (!loop) return run_graph(nominal, relaxed, f, steps, s);  // mid / long horizons, reproducible or debug mode
-  return mpcqp::enqueue_fused_loop(nominal, relaxed, loop, "k_fleet_loop", true, {nullptr, f, steps}, s);
+  return mpcqp::enqueue_fused_loop(nominal, relaxed, loop, "k_fleet_loop", MPCQP_LAUNCH_LOOP, true,
+                                   {nullptr, f, steps}, s);
 }
 
 int mpcqp_fleet_loop_mixed(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const int32_t* cls, int steps,
@@ -350,23 +353,45 @@ int mpcqp_fleet_loop_mixed(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fle
   mpcqp::LoopLaunch L{nullptr, f, steps};
   L.cls = cls;
   L.K = K;
-  return mpcqp::enqueue_fused_loop(nominal, relaxed, loop, "k_fleet_loop_mixed", false, L, s);
+  return mpcqp::enqueue_fused_loop(nominal, relaxed, loop, "k_fleet_loop_mixed", MPCQP_LAUNCH_LOOP_MIXED, false, L, s);
 }
 
-int mpcqp_fleet_loop_warm(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, int steps, int guess_passes,
-                          void* stream) {
+// mpcqp_fleet_loop_warm (carry == nullptr) and mpcqp_fleet_loop_warm_carry after their own argument
+// checks; `who` names the caller in the refusal.  One vehicle per wave without a carried guess is
+// k_fleet_loop_warm; a carried guess, or two vehicles per wave (MPCQP_PAIR_ON, N <= 15), is
+// k_fleet_loop_warm_carry.
+static int fleet_loop_warm(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, int steps, int guess_passes,
+                           double* carry, const char* who, void* stream) {
   int rc = check_fleet(nominal, relaxed, f);
   if (rc) return rc;
   if (steps < 0) return fail(MPCQP_E_ARG, "steps must be >= 0");
   // the fused one-wave kernel only; refused before anything is enqueued or invalidated
   const mpcqp::fleet_loop_t loop = mpcqp::fused_loop(nominal, relaxed, &mpcqp::HorizonKernels::loop_warm);
-  if (!loop)
-    return fail(MPCQP_E_HORIZON, "mpcqp_fleet_loop_warm runs the fused one-wave loop only (N <= 32, fast mode, no "
-                                 "debug_state): the stepped fleet takes no guess");
+  const mpcqp::fleet_loop_t loop_carry = mpcqp::fused_loop(nominal, relaxed, &mpcqp::HorizonKernels::loop_warm_carry);
+  if (!loop || !loop_carry)
+    return fail(MPCQP_E_HORIZON, std::string(who) + " runs the fused one-wave loop only (N <= 32, fast mode, no "
+                                                    "debug_state): the stepped fleet takes no guess");
   if (f->vehicles == 0 || steps == 0) return MPCQP_OK;
   mpcqp::LoopLaunch L{nullptr, f, steps};
   L.guess_passes = guess_passes;
-  return mpcqp::enqueue_fused_loop(nominal, relaxed, loop, "k_fleet_loop_warm", false, L, static_cast<hipStream_t>(stream));
+  L.carry = carry;
+  L.tr.pair = mpcqp::use_pairs_warm(nominal);
+  const bool carry_kernel = carry || L.tr.pair;
+  return mpcqp::enqueue_fused_loop(nominal, relaxed, carry_kernel ? loop_carry : loop,
+                                   carry_kernel ? "k_fleet_loop_warm_carry" : "k_fleet_loop_warm",
+                                   carry ? MPCQP_LAUNCH_LOOP_WARM_CARRY : MPCQP_LAUNCH_LOOP_WARM, false, L,
+                                   static_cast<hipStream_t>(stream));
+}
+
+int mpcqp_fleet_loop_warm(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, int steps, int guess_passes,
+                          void* stream) {
+  return fleet_loop_warm(nominal, relaxed, f, steps, guess_passes, nullptr, "mpcqp_fleet_loop_warm", stream);
+}
+
+int mpcqp_fleet_loop_warm_carry(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, int steps, int guess_passes,
+                                double* U_carry, void* stream) {
+  if (!U_carry) return fail(MPCQP_E_ARG, "null U_carry");
+  return fleet_loop_warm(nominal, relaxed, f, steps, guess_passes, U_carry, "mpcqp_fleet_loop_warm_carry", stream);
 }
 
 int mpcqp_fleet_run(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, int steps, int use_graph,

@@ -1761,7 +1761,7 @@ struct Guess<false> {
 // One QP through setup -> ADMM (+ early polish attempts) -> final polish -> outputs on the calling
 // wave, for k_solve_pair, k_solve_mixed, k_fleet_loop and k_serve (no debug state): returns the status,
 // Ulane = the lane's U entry (lanes 0 and N: u0).  k_solve runs the same driver inline (below).
-// Warm (k_solve_warm, k_fleet_loop_warm; fused K1 only): g.lane is the lane's entry of a caller's U
+// Warm (k_solve_warm, k_solve_pair_warm, k_fleet_loop_warm, k_fleet_loop_warm_carry; fused K1 only): g.lane is the lane's entry of a caller's U
 // (guess_lane).  A usable guess (every entry finite, g.passes > 0, method ADMM) gets one polish
 // of at most min(g.passes, polish_max_iter) passes before ADMM, as the loop's first trip: the
 // polish returns the exact optimum from wherever it converges, so a hit ends the solve with no ADMM
@@ -2103,6 +2103,64 @@ __global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_solve_warm(mpcqp
                                       iterso, activeo, U, Guess<true>{g, guess_passes});
 }
 
+// PairGuessWin: two QPs per wave from a caller's guess (k_solve_pair_warm): ServeWin exactly (the lane
+// within the half, opaque); a type of its own for ClassWin's reason.
+struct PairGuessWin {
+  static constexpr bool kFleet = false;
+  int ln;
+  __device__ __forceinline__ int lane() const { return ln; }
+};
+
+// ------------------------------------------------------------------ K2 from a caller's guess, two QPs per wave
+// mpcqp_solve_warm under MPCQP_PAIR_ON (N <= 15): k_solve_pair's layout (half h of workgroup w solves QP
+// 2w + h with the half-wave lane policy and its own LDS block) with k_solve_warm's guess, each half
+// through solve_one's warm driver on its own: one half may hit while the other misses, holds an unusable
+// guess or is absent (b >= B returns alone).  What then differs between the halves -- g.pending, g.now,
+// the attempt's pass limit, the miss reset of S, the block under `if (g.pending)` -- is a function of
+// threadIdx.x >> 5 through Lanes<true>::ballot, so every branch on it is an exec-masked one, and every
+// cross-lane read on those paths (guess_lane's scan: row shifts and row_bcast:15 into rows 1 / 3; Cmul's
+// shr1: cut at the half boundary) has its source lanes in the reader's half and its result pinned where
+// it is computed (Lanes<true>).  Results: k_solve_warm's bit for bit.  A half's lanes ln < 2N read row b of
+// U_guess here, before anything is written: U_guess may be the U output.
+template <int N>
+__global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_solve_pair_warm(mpcqp_params p, int B,
+                                                           const double* __restrict__ in_x0,
+                                                           const double* __restrict__ in_ref,
+                                                           const double* __restrict__ in_up, const double* U_guess,
+                                                           int guess_passes, double* __restrict__ u0o,
+                                                           double* __restrict__ Xo, double* Uo,
+                                                           int32_t* __restrict__ statuso,
+                                                           int32_t* __restrict__ iterso,
+                                                           uint8_t* __restrict__ activeo) {
+  static_assert(2 * N <= 30, "two QPs per wave need n = 2N <= 30 (a padding lane or two per half)");
+  __shared__ SolveLds<N, true> sm[2];
+  const int h = threadIdx.x >> 5;
+  const int b = 2 * blockIdx.x + h;
+  if (b >= B) return;  // that half only: the other QP runs on
+  int ln = threadIdx.x & 31;
+  asm volatile("" : "+v"(ln));
+  const double g = ln < 2 * N ? U_guess[(size_t)b * (2 * N) + ln] : 0.0;
+  double U;
+  solve_one<N, PairGuessWin, true, true>(p, b, nullptr, in_x0, in_ref, in_up, PairGuessWin{ln}, sm[h], u0o, Xo, Uo,
+                                         statuso, iterso, activeo, U, Guess<true>{g, guess_passes});
+}
+
+// FleetCarryWin: a vehicle of k_fleet_loop_warm_carry: FleetWin exactly; a type of its own for ClassWin's
+// reason (solve_one's warm driver shared with k_fleet_loop_warm changed that kernel's code generation at
+// every horizon).
+struct FleetCarryWin : FleetWin {};
+
+// The carried guess of k_fleet_loop_warm_carry in fleet_loop_body: the V x 2 x N buffer (nullable) and
+// whether a solve of this launch was accepted.  The loops without it carry the empty one (no variable of
+// its own in the body: Guess<false>'s reason).
+template <bool Carry>
+struct CarryRow {
+  double* rows = nullptr;
+  bool accepted = false;
+};
+template <>
+struct CarryRow<false> {};
+
 // ------------------------------------------------------------------ fused closed loop
 // Every vehicle of a fleet runs `steps` iterations of the loop body of TrajectoryTracker.track
 // (control_stage.py:100-150) on its own wave, with no kernel boundary between steps: the window
@@ -2119,10 +2177,15 @@ __global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_solve_warm(mpcqp
 // doubles of loop state in LDS, sm its solver LDS.
 // Warm (k_fleet_loop_warm): each solve of a step starts from the U of the step before, shifted one step
 // down (solve_one's warm driver); Ug, that U's lane value, is the only state it adds to the step loop.
-template <int N, bool Pair, bool Warm = false>
+// Carry (k_fleet_loop_warm_carry; with Warm): a RUNNING vehicle's Ug starts from row b of carry.rows
+// instead of NaN, and after the loop the last accepted U goes back there, unshifted (the shift stays at
+// the read inside the step loop) -- only if a solve of this launch was accepted.  Null rows: neither.
+template <int N, bool Pair, bool Warm = false, bool Carry = false>
 __device__ __forceinline__ void fleet_loop_body(const mpcqp_params* __restrict__ P, const mpcqp_fleet& f, int steps,
                                                 const mpcqp::LoopTrigger& tr, int b, int lane,
-                                                SolveLds<N, Pair>& sm, double* const ls, int guess_passes = 0) {
+                                                SolveLds<N, Pair>& sm, double* const ls, int guess_passes = 0,
+                                                CarryRow<Carry> carry = {}) {
+  static_assert(Warm || !Carry, "the carried guess belongs to the warm loop");
   using LN = Lanes<Pair>;
   const int V = f.vehicles;
   int phase = f.phase[b];
@@ -2154,6 +2217,9 @@ __device__ __forceinline__ void fleet_loop_body(const mpcqp_params* __restrict__
   // warm: the accepted solve's U of the step before, by lane; NaN (no step yet in this launch) is an
   // unusable guess, so a vehicle's first step is cold
   [[maybe_unused]] double Ug = __builtin_nan("");
+  if constexpr (Carry) {  // the guess a launch before left; a row with a non-finite entry is unusable (solve_one)
+    if (carry.rows && lane < 2 * N) Ug = carry.rows[(size_t)b * (2 * N) + lane];
+  }
   for (int s = 0; s < steps; ++s) {
     // k_fleet_build's validation of the loop state, before any indexed access
     const bool bad_ref = len < 1 || len > f.ref_stride || pidx < 0;
@@ -2182,10 +2248,17 @@ __device__ __forceinline__ void fleet_loop_body(const mpcqp_params* __restrict__
         double up = LN::shl1(Ug);
         asm volatile("" : "+v"(up));  // pinned: the shift runs on every lane, not inside the select below
         const double g = (ln == N - 1 || ln == 2 * N - 1) ? Ug : up;
-        st = solve_one<N, FleetWin, Pair, true>(p, b, nullptr, nullptr, nullptr, nullptr, win, sm,
-                                                f.u0 + (size_t)relax * V * 2, f.X, nullptr,
-                                                f.status + (size_t)relax * V, nullptr, nullptr, Ul,
-                                                Guess<true>{g, guess_passes});
+        if constexpr (Carry) {
+          st = solve_one<N, FleetCarryWin, Pair, true>(p, b, nullptr, nullptr, nullptr, nullptr, FleetCarryWin{win}, sm,
+                                                       f.u0 + (size_t)relax * V * 2, f.X, nullptr,
+                                                       f.status + (size_t)relax * V, nullptr, nullptr, Ul,
+                                                       Guess<true>{g, guess_passes});
+        } else {
+          st = solve_one<N, FleetWin, Pair, true>(p, b, nullptr, nullptr, nullptr, nullptr, win, sm,
+                                                  f.u0 + (size_t)relax * V * 2, f.X, nullptr,
+                                                  f.status + (size_t)relax * V, nullptr, nullptr, Ul,
+                                                  Guess<true>{g, guess_passes});
+        }
       } else {
         st = solve_one<N, FleetWin, Pair>(p, b, nullptr, nullptr, nullptr, nullptr, win, sm,
                                           f.u0 + (size_t)relax * V * 2, f.X, nullptr,
@@ -2197,6 +2270,7 @@ __device__ __forceinline__ void fleet_loop_body(const mpcqp_params* __restrict__
         which = relax;
         U = Ul;
         if constexpr (Warm) Ug = Ul;
+        if constexpr (Carry) carry.accepted = true;
         break;
       }
     }
@@ -2241,6 +2315,9 @@ __device__ __forceinline__ void fleet_loop_body(const mpcqp_params* __restrict__
   }
   if (lane < 4) f.state[(size_t)b * 4 + lane] = ls[lane];
   else if (lane < 6) f.u_prev[(size_t)b * 2 + lane - 4] = ls[lane];
+  if constexpr (Carry) {  // a vehicle that left before any accept leaves its row as it was
+    if (carry.rows && carry.accepted && lane < 2 * N) carry.rows[(size_t)b * (2 * N) + lane] = Ug;
+  }
   if (lane == 0) {
     f.path_idx[b] = pidx;
     f.steps[b] = k;
@@ -2321,6 +2398,31 @@ __global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_fleet_loop_warm(
   if (b < 0 || b >= f.vehicles) return;
   const mpcqp::LoopTrigger off{0.0, 0, nullptr, nullptr};
   fleet_loop_body<N, false, true>(P, f, steps, off, b, lane, sm, ls, guess_passes);
+}
+
+// ------------------------------------------------------------------ fused closed loop, warm, guess carried
+// mpcqp_fleet_loop_warm_carry, and mpcqp_fleet_loop_warm under MPCQP_PAIR_ON (U_carry null):
+// k_fleet_loop_warm's body with the guess carried across launches (fleet_loop_body's Carry).  Pair
+// (N <= 15): two vehicles per wave, dispatched exactly as k_fleet_loop<N, true> -- slot 2 blockIdx.x + h
+// (V at odd V: that half returns alone), vehicle order[slot].  The halves of a wave hit, miss and leave
+// the step loop apart (k_solve_pair_warm); the shift of Ug (Lanes<true>::shl1) is cut at the half boundary
+// and pinned outside the select that follows it.  No replan trigger.
+template <int N, bool Pair = false>
+__global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_fleet_loop_warm_carry(
+    const mpcqp_params* __restrict__ P, mpcqp_fleet f, int steps, int guess_passes, const int32_t* __restrict__ order,
+    double* U_carry) {
+  static_assert(!Pair || 2 * N <= 30, "two vehicles per wave need n = 2N <= 30");
+  __shared__ SolveLds<N, Pair> smv[Pair ? 2 : 1];
+  __shared__ double lsv[Pair ? 12 : 6];  // loop state: x[4], u_prev[2] (per half)
+  const int h = Pair ? (int)(threadIdx.x >> 5) : 0;
+  SolveLds<N, Pair>& sm = smv[h];
+  double* const ls = lsv + 6 * h;
+  const int slot = Pair ? 2 * (int)blockIdx.x + h : (int)blockIdx.x;  // pair: may be V (odd V)
+  const int b = (order && slot < f.vehicles) ? order[slot] : slot;
+  const int lane = Pair ? (int)(threadIdx.x & 31) : (int)threadIdx.x;
+  if (b < 0 || b >= f.vehicles) return;
+  const mpcqp::LoopTrigger off{0.0, 0, nullptr, nullptr};
+  fleet_loop_body<N, Pair, true, true>(P, f, steps, off, b, lane, sm, ls, guess_passes, CarryRow<true>{U_carry});
 }
 
 // ------------------------------------------------------------------ B = 1 server
@@ -2464,6 +2566,27 @@ void launch_fleet_loop_warm(hipStream_t s, const LoopLaunch& L) {
   hipLaunchKernelGGL(k_fleet_loop_warm<N>, dim3(L.f->vehicles), dim3(kWave), 0, s, L.P, *L.f, L.steps, L.guess_passes,
                      L.tr.order);
 }
+// the warm loop with the carried guess (L.carry, nullable); L.tr.pair: two vehicles per wave
+template <int N>
+void launch_fleet_loop_warm_carry(hipStream_t s, const LoopLaunch& L) {
+  const mpcqp_fleet& f = *L.f;
+  if constexpr (N <= kPairMaxHorizon) {
+    if (L.tr.pair) {
+      hipLaunchKernelGGL((k_fleet_loop_warm_carry<N, true>), dim3((f.vehicles + 1) / 2), dim3(kWave), 0, s, L.P, f,
+                         L.steps, L.guess_passes, L.tr.order, L.carry);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((k_fleet_loop_warm_carry<N, false>), dim3(f.vehicles), dim3(kWave), 0, s, L.P, f, L.steps,
+                     L.guess_passes, L.tr.order, L.carry);
+}
+// two QPs per wave from a caller's guess (N <= kPairMaxHorizon)
+template <int N>
+void launch_solve_pair_warm(hipStream_t s, const Launch& L) {
+  static_assert(N <= kPairMaxHorizon, "a half-wave holds n = 2N <= 30 variables");
+  hipLaunchKernelGGL(k_solve_pair_warm<N>, dim3((L.B + 1) / 2), dim3(kWave), 0, s, *L.p, L.B, L.x0, L.ref, L.u_prev,
+                     L.guess, L.guess_passes, L.u0, L.X, L.U, L.st, L.it, L.ac);
+}
 // two QPs per wave (N <= kPairMaxHorizon, fused K1, no debug state)
 template <int N>
 void launch_solve_pair(hipStream_t s, const Launch& L) {
@@ -2479,8 +2602,11 @@ template <int LO, int HI>
 int register_horizons() {
   HorizonKernels k{&launch_solve<LO>, &launch_solve_mixed<LO>, nullptr, &launch_serve<LO>, &launch_fleet_loop<LO>,
                    &launch_fleet_loop_mixed<LO>, &launch_solve_warm<LO>, &launch_fleet_loop_warm<LO>,
-                   &launch_serve_warm<LO>};
-  if constexpr (LO <= kPairMaxHorizon) k.pair = &launch_solve_pair<LO>;
+                   &launch_serve_warm<LO>, nullptr, &launch_fleet_loop_warm_carry<LO>};
+  if constexpr (LO <= kPairMaxHorizon) {
+    k.pair = &launch_solve_pair<LO>;
+    k.pair_warm = &launch_solve_pair_warm<LO>;
+  }
   register_horizon(LO, k);
   if constexpr (LO < HI) return register_horizons<LO + 1, HI>();
   return 0;

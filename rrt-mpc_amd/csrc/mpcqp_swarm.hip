@@ -279,7 +279,7 @@ int mpcqp_swarm_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f,
     return mpcqp_swarm_run(nominal, relaxed, f, s, f->max_steps, 1, stream);
   const mpcqp::LoopTrigger tr{s->replan_distance, s->max_replans, s->replans, s->start_goal};
   for (int r = 0; r <= s->max_replans; ++r) {
-    rc = mpcqp::enqueue_fused_loop(nominal, relaxed, loop, "k_fleet_loop", true, {nullptr, f, f->max_steps, tr}, st);
+    rc = mpcqp::enqueue_fused_loop(nominal, relaxed, loop, "k_fleet_loop", MPCQP_LAUNCH_LOOP, true, {nullptr, f, f->max_steps, tr}, st);
     if (rc) return rc;
     if (r < s->max_replans && (rc = enqueue_replan(f, s, st, false)) != MPCQP_OK) return rc;
   }

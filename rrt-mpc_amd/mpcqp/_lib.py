@@ -41,6 +41,12 @@ ABI_VERSION = 9  # MPCQP_ABI_VERSION (include/mpcqp.h)
 PAIR_OFF, PAIR_ON, PAIR_AUTO = 0, 1, 2
 PAIRING_MODES = {"off": PAIR_OFF, "on": PAIR_ON, "auto": PAIR_AUTO}
 E_DEVICE = -6  # MPCQP_E_DEVICE: a fault surfaced at a stream synchronisation
+# mpcqp_launch_info: info[0], the kind of the last solver launch recorded on a workspace (MPCQP_LAUNCH_*)
+(LAUNCH_NONE, LAUNCH_SOLVE, LAUNCH_SOLVE_MIXED, LAUNCH_SOLVE_WARM, LAUNCH_LOOP, LAUNCH_LOOP_MIXED, LAUNCH_LOOP_WARM,
+ LAUNCH_LOOP_WARM_CARRY) = range(8)
+LAUNCH_KINDS = {LAUNCH_NONE: "none", LAUNCH_SOLVE: "solve", LAUNCH_SOLVE_MIXED: "solve_mixed",
+                LAUNCH_SOLVE_WARM: "solve_warm", LAUNCH_LOOP: "loop", LAUNCH_LOOP_MIXED: "loop_mixed",
+                LAUNCH_LOOP_WARM: "loop_warm", LAUNCH_LOOP_WARM_CARRY: "loop_warm_carry"}
 # warm start (mpcqp_solve_warm, mpcqp_fleet_loop_warm): polish passes the guess's attempt may take
 DEFAULT_GUESS_PASSES = 8  # the best of 1, 2, 3, 5, 8 at 4096 vehicles, N = 20 (profiles/warm_start/)
 
@@ -325,6 +331,9 @@ _SYMBOLS = {
                          ctypes.c_int),
     "mpcqp_fleet_loop_warm": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MpcqpFleet), ctypes.c_int,
                                ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
+    "mpcqp_fleet_loop_warm_carry": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MpcqpFleet), ctypes.c_int,
+                                     ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+    "mpcqp_launch_info": ([ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
     "mpcqp_stage_guess": ([ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)], ctypes.c_int),
     "mpcqp_solve_staged_warm": ([ctypes.c_void_p, ctypes.c_int], ctypes.c_int),
     "mpcqp_solve_served_warm": ([ctypes.c_void_p, ctypes.c_int], ctypes.c_int),
@@ -338,6 +347,15 @@ def build_id() -> str:
 
 def exported_symbols():
     return list(_SYMBOLS)
+
+
+def launch_info(ws) -> dict:
+    """mpcqp_launch_info of a workspace handle as a dict: kind (MPCQP_LAUNCH_*), its name, QPs or vehicles
+    per wave, workgroups launched, and the launch's B or V.  Host bookkeeping: no device call."""
+    info = (ctypes.c_int32 * 4)()
+    check(lib().mpcqp_launch_info(ws, info), "mpcqp_launch_info")
+    return {"kind": int(info[0]), "name": LAUNCH_KINDS.get(int(info[0]), "?"), "per_wave": int(info[1]),
+            "workgroups": int(info[2]), "count": int(info[3])}
 
 
 def lib() -> ctypes.CDLL:

@@ -129,7 +129,9 @@ class BatchedMPCController:
     device) or float64 device tensors (used in place).
 
     ``pairing`` ("auto", "on", "off"): two QPs per wave for horizons N <= 15 (``mpcqp_set_pairing``;
-    the same results bit for bit).  "auto" pairs a launch with more QPs than the GPU has wave slots.
+    the same results bit for bit).  "auto" pairs a launch with more QPs than the GPU has wave slots;
+    a warm launch (``solve_batch(..., U_guess=...)``, the warm fleet loops) pairs under "on" only.
+    ``launch_info()`` tells what the last launch did.
 
     Mixed batches: ``set_classes([params_0, ..., params_{K-1}])`` gives the workspace a table of K
     parameter blocks of this horizon, and ``solve_batch(..., classes=cls)`` solves QP b under block
@@ -187,6 +189,12 @@ class BatchedMPCController:
         _lib.check(self._L.mpcqp_set_pairing(self._ws, _lib.PAIRING_MODES[mode]), "mpcqp_set_pairing")
         self.pairing = mode
 
+    def launch_info(self) -> dict:
+        """What the last solver launch recorded on this controller's workspace did (``mpcqp_launch_info``;
+        no device call): ``{"kind": _lib.LAUNCH_*, "name", "per_wave": 1 or 2, "workgroups", "count": B or V}``.
+        ``kind`` is ``_lib.LAUNCH_NONE`` before any launch and after ``set_params``."""
+        return _lib.launch_info(self._ws)
+
     def set_classes(self, params_list, settings=None, *, method=None) -> None:
         """The parameter blocks ("classes") of mixed batches: ``params_list[k]`` is block k
         (``mpcqp_set_classes``; synchronous).  ``settings``: one dict of solver settings for all
@@ -240,7 +248,10 @@ class BatchedMPCController:
         passes (default ``_lib.DEFAULT_GUESS_PASSES``) from its guess; a hit returns the exact optimum
         with ``iters[:, 0] == 0``, a miss or an unusable guess (a non-finite entry, ``guess_passes <= 0``)
         runs the cold solve unchanged.  The previous ``U`` shifted one step is the usual guess; the
-        returned ``U`` tensor itself may be passed.  Not with ``classes``; horizons <= 32 in fast mode."""
+        returned ``U`` tensor itself may be passed.  Not with ``classes``; horizons <= 32 in fast mode.
+        Under ``pairing="on"`` (N <= 15) the guess pairs too: two QPs per wave, each half with its own
+        attempt, the results those of ``pairing="off"`` bit for bit; ``"auto"`` keeps a warm launch at
+        one QP per wave."""
         torch = self._torch
         N = self.horizon
         B = int(x0.shape[0])

@@ -115,15 +115,27 @@ class FleetTracker:
     start from the ``U`` of its step before, shifted one step (``mpcqp_fleet_loop_warm``): one polish
     attempt of at most ``guess_passes`` passes (default ``_lib.DEFAULT_GUESS_PASSES``) before ADMM, which
     a hit skips; a miss runs the cold solve unchanged.  Results equal the cold loop's to rounding.
+    A vehicle's first step of every launch is cold, so a tracker stepped in short launches loses the guess
+    each time.  ``carry_guess=True`` (with ``warm_start=True``) keeps it: the tracker owns a ``U_carry``
+    tensor (``max_vehicles x 2 x N``, ``buffers()["U_carry"]``, NaN-filled for the loaded vehicles by every
+    reset) and ``step`` calls ``mpcqp_fleet_loop_warm_carry``, so a run split into launches of any sizes
+    equals the same run in one warm launch bit for bit.  Off by default: a split run's results then differ
+    from the uncarried ones at rounding level.
+
+    ``pairing`` ("auto", "on", "off"; passed on to both controllers): two vehicles per wave for N <= 15 in
+    the fused loops, the same buffers bit for bit.  The warm loops pair under "on" only; "auto" leaves
+    them at one vehicle per wave.
     """
 
     warm_start = False
+    carry_guess = False
+    _carry = None
     guess_passes = _lib.DEFAULT_GUESS_PASSES
 
     def __init__(self, mpc, *, map_resolution: float, max_vehicles: int, max_ref_len: int,
                  device=None, use_graph: bool = True, fused: bool = False,
                  relaxed_settings: Optional[dict] = None, params=None, warm_start: bool = False,
-                 guess_passes: Optional[int] = None, **settings) -> None:
+                 guess_passes: Optional[int] = None, carry_guess: bool = False, **settings) -> None:
         import torch
 
         from ..control.mpc_controller import BatchedMPCController
@@ -133,7 +145,10 @@ class FleetTracker:
             raise ValueError("warm_start needs fused=True: only the fused loop carries a guess from step to step")
         if guess_passes is not None and not warm_start:
             raise ValueError("guess_passes needs warm_start=True")
+        if carry_guess and not warm_start:
+            raise ValueError("carry_guess needs warm_start=True: the carried guess belongs to the warm loop")
         self.warm_start = bool(warm_start)
+        self.carry_guess = bool(carry_guess)
         self.guess_passes = _lib.DEFAULT_GUESS_PASSES if guess_passes is None else int(guess_passes)
         self._torch = torch
         self.mpc = mpc
@@ -156,6 +171,9 @@ class FleetTracker:
                                              device=self._nominal.device, **rs)
         self.device = self._nominal.device
         self._L = _lib.lib()
+        # the guess carried across launches (mpcqp_fleet_loop_warm_carry): NaN = none yet, a cold first step
+        self._carry = (torch.full((self.max_vehicles, 2, self.horizon), float("nan"), dtype=torch.float64,
+                                  device=self.device) if self.carry_guess else None)
         self._bufs = None
         self._fleet = None
         self.vehicles = 0
@@ -281,6 +299,9 @@ class FleetTracker:
             setattr(f, name, t.data_ptr())
         # the vehicles' class indices (mpcqp_fleet_loop_mixed's argument, not a member of mpcqp_fleet)
         b["cls"] = cls if cls is not None else torch.zeros((max(V, 1),), dtype=i32, **dev)
+        if self._carry is not None:  # a new run starts without a guess
+            self._carry[:V].fill_(float("nan"))
+            b["U_carry"] = self._carry
         self._bufs = b
         self._fleet = f
         self.vehicles = V
@@ -344,6 +365,8 @@ class FleetTracker:
         fleet = (self._nominal._ws, self._relaxed._ws, ctypes.byref(self._fleet))
         if self.num_classes:  # a class per vehicle (set_classes: fused only)
             call, args = "mpcqp_fleet_loop_mixed", (self._bufs["cls"].data_ptr(), int(steps))
+        elif self.carry_guess:  # warm, and the first step of this launch from the last step of the launch before
+            call, args = "mpcqp_fleet_loop_warm_carry", (int(steps), self.guess_passes, self._carry.data_ptr())
         elif self.warm_start:  # fused, each step's solves started from the step before (cold at every launch)
             call, args = "mpcqp_fleet_loop_warm", (int(steps), self.guess_passes)
         elif self.fused:

@@ -13,6 +13,11 @@ reference-style host loop (TrajectoryTracker.track, one B=1 solve per step) on o
 back (mpcqp_fleet_loop each, --pairing applies to them); K = 1 measures the mixed kernel against the plain
 fused loop.  The two sides alternate within every repeat, first in one order, then in the other; the
 references are loaded before the timed window, which holds the loop launches up to a synchronise.
+
+--warm: the cold fused loop against the warm-started one, interleaved in one process (warm_bench).  With
+several --pairing modes every mode gets a cold and a warm side (--pairing on off: cold paired, warm paired,
+cold unpaired, warm unpaired); --launch-steps K ... adds the warm loop as launches of K steps, with and
+without the carried guess (mpcqp_fleet_loop_warm_carry).
 """
 from __future__ import annotations
 
@@ -117,9 +122,14 @@ def mixed_bench(a) -> None:
 
 
 def warm_bench(a) -> None:
-    """The cold fused loop (--pairing applies to it) against the warm-started one (mpcqp_fleet_loop_warm) at
-    each --guess-passes value, on the same vehicles: the sides alternate within every repeat, the order
-    rotating from repeat to repeat; the timed window holds the loop launch up to a synchronise."""
+    """The cold fused loop against the warm-started one (mpcqp_fleet_loop_warm) at each --guess-passes value,
+    on the same vehicles: the sides alternate within every repeat, the order rotating from repeat to repeat;
+    the timed window holds the loop launches up to a synchronise.
+    --pairing takes one mode or several.  One: the sides are "cold" and "warm:P" under it (a warm loop pairs
+    under "on" only).  Several: a cold and a warm side per mode, "cold/on", "warm:P/on", ...
+    --launch-steps K ...: the warm loop as ceil(steps / K) launches of K steps each (no host check between
+    them), without the carried guess ("warm:P/launch K": cold at every launch) and with it ("carry:P/launch K",
+    mpcqp_fleet_loop_warm_carry), under the first --pairing mode, beside that mode's single launch."""
     import torch
 
     from mpcqp import scenarios
@@ -128,7 +138,7 @@ def warm_bench(a) -> None:
 
     dev = torch.device("cuda:0")
     out = {"metric": "closed-loop vehicle-steps/s, loop launch only", "horizon": a.horizon, "sim_steps": a.steps,
-           "pairing_of_cold": a.pairing, "plan": a.plan, "reps": a.reps, "runs": []}
+           "pairing": a.pairing, "launch_steps": a.launch_steps, "plan": a.plan, "reps": a.reps, "runs": []}
     mpc = MPCConfig(horizon=a.horizon, sim_steps=a.steps)
     for V in a.vehicles:
         if a.plan == "config1":  # the default plan itself, every vehicle from its start
@@ -144,30 +154,46 @@ def warm_bench(a) -> None:
 
             ref_len = len(build_reference(paths[0], mpc.v_px_s, a.horizon, mpc.dt))
         kw = dict(map_resolution=0.8, max_vehicles=V, max_ref_len=ref_len, device=dev, fused=True)
-        sides = {"cold": FleetTracker(mpc, pairing=a.pairing, **kw)}
-        for gp in a.guess_passes:
-            sides[f"warm:{gp}"] = FleetTracker(mpc, warm_start=True, guess_passes=gp, **kw)
+        sides, chunk = {}, {}
+        for mode in a.pairing:
+            tag = f"/{mode}" if len(a.pairing) > 1 else ""
+            sides[f"cold{tag}"] = FleetTracker(mpc, pairing=mode, **kw)
+            for gp in a.guess_passes:
+                sides[f"warm:{gp}{tag}"] = FleetTracker(mpc, warm_start=True, guess_passes=gp, pairing=mode, **kw)
+        for K in a.launch_steps:
+            for gp in a.guess_passes:
+                for what, carry in (("warm", False), ("carry", True)):
+                    k = f"{what}:{gp}/launch {K}"
+                    sides[k] = FleetTracker(mpc, warm_start=True, guess_passes=gp, carry_guess=carry,
+                                            pairing=a.pairing[0], **kw)
+                    chunk[k] = K
         names = list(sides)
+        first_cold = names[0]
         times = {k: [] for k in names}
         for r in range(a.reps + 1):  # repeat 0 warms up
             for ft in sides.values():
                 ft.reset_from_plans(paths, starts, goals, device_reference=a.plan != "config1")
             for k in names[r % len(names):] + names[:r % len(names)]:
+                K = chunk.get(k, a.steps)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                sides[k].step(a.steps)
+                for _ in range(-(-a.steps // K)):
+                    sides[k].step(K)
                 torch.cuda.synchronize()
                 if r:
                     times[k].append(time.perf_counter() - t0)
         res = {k: ft.result() for k, ft in sides.items()}
-        cold = res["cold"]
+        launches = {k: sides[k]._nominal.launch_info() for k in names}
+        cold = res[first_cold]
         run = {"vehicles": V, "vehicle_steps": int(cold.steps.sum()), "goal_reached": int((cold.phase == 1).sum()),
                "aborted": int((cold.phase == 2).sum())}
         for k in names:
             ts, rk = times[k], res[k]
             med = float(np.median(ts))
             run[k] = {"seconds_median": med, "seconds_min": min(ts), "seconds_max": max(ts), "seconds": ts,
-                      "value": int(rk.steps.sum()) / med, "time_over_cold": med / float(np.median(times["cold"])),
+                      "value": int(rk.steps.sum()) / med, "time_over_cold": med / float(np.median(times[first_cold])),
+                      "launches": -(-a.steps // chunk.get(k, a.steps)), "per_wave": launches[k]["per_wave"],
+                      "workgroups": launches[k]["workgroups"],
                       "same_steps_and_phases": bool((rk.steps == cold.steps).all() and (rk.phase == cold.phase).all()),
                       "max_state_diff_vs_cold": max((float(np.abs(x - y).max()) for x, y in zip(rk.states, cold.states)
                                                      if len(x) and x.shape == y.shape), default=0.0)}
@@ -185,8 +211,12 @@ def main() -> None:
     ap.add_argument("--horizon", type=int, default=15)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--fused", action="store_true", help="mpcqp_fleet_loop: one launch for the whole loop")
-    ap.add_argument("--pairing", default="auto", choices=["auto", "on", "off"],
-                    help="two vehicles per wave for N <= 15 (mpcqp_set_pairing)")
+    ap.add_argument("--pairing", nargs="+", default=["auto"], choices=["auto", "on", "off"],
+                    help="two vehicles per wave for N <= 15 (mpcqp_set_pairing); with --warm several modes may be "
+                         "given: a cold and a warm side per mode")
+    ap.add_argument("--launch-steps", type=int, nargs="+", default=[],
+                    help="with --warm: also run the warm loop as launches of K steps, with and without the carried "
+                         "guess (mpcqp_fleet_loop_warm_carry)")
     ap.add_argument("--classes", type=int, default=0,
                     help="K > 0: one mixed fused launch (mpcqp_fleet_loop_mixed) against K homogeneous fused launches")
     ap.add_argument("--warm", action="store_true",
@@ -196,6 +226,12 @@ def main() -> None:
     ap.add_argument("--plan", default="fleet5", choices=["fleet5", "config1"],
                     help="with --warm: RRT*-branch plans, or every vehicle on the default (config-1) plan")
     a = ap.parse_args()
+    if any(K < 1 for K in a.launch_steps):
+        ap.error("--launch-steps takes step counts >= 1")
+    if not a.warm:
+        if len(a.pairing) > 1 or a.launch_steps:
+            ap.error("several --pairing modes and --launch-steps go with --warm")
+        a.pairing = a.pairing[0]
     if a.classes:
         mixed_bench(a)
         return
