@@ -283,7 +283,7 @@ int mpcqp_solve_served_warm(mpcqp_ws* ws, int guess_passes);
  * built in the solve) or two vehicles of the fused loop (mpcqp_fleet_loop, mpcqp_swarm_loop), with
  * the results of the one-QP-per-wave kernel bit for bit.  MPCQP_PAIR_AUTO (the default) pairs once
  * a launch has more QPs than the device has wave slots (8 per CU); ON / OFF force it.  The warm calls
- * (mpcqp_solve_warm, mpcqp_fleet_loop_warm, mpcqp_fleet_loop_warm_carry) pair under ON only: AUTO
+ * (mpcqp_solve_warm, mpcqp_fleet_loop_warm, mpcqp_fleet_loop_warm_carry, mpcqp_swarm_loop_warm) pair under ON only: AUTO
  * leaves them at one per wave.  Ignored where
  * the one-wave kernel does not run (N > 15, reproducible, debug_state).  No counterpart in the
  * reference (OSQP solves one QP per call). */
@@ -420,8 +420,8 @@ int mpcqp_fleet_loop_mixed(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fle
  * Argument checks, the device's validation of the loop state, the exits, the longest-first dispatch and
  * the invalidation of both workspaces' builds are mpcqp_fleet_loop's.  The fused loop only -- N <= 32 in
  * fast mode without debug_state; other parameter blocks return MPCQP_E_HORIZON, and then nothing is
- * enqueued and nothing invalidated.  The replan trigger is off.  Out of scope: the stepped fleet, mixed
- * classes and the swarm.
+ * enqueued and nothing invalidated.  The replan trigger is off (the swarm's warm loop is
+ * mpcqp_swarm_loop_warm).  Out of scope: the stepped fleet and mixed classes.
  * Pairing (mpcqp_set_pairing on `nominal`): MPCQP_PAIR_ON runs two vehicles per wave where the paired
  * kernel exists (N <= 15), dispatched as the paired mpcqp_fleet_loop, every buffer equal to the
  * one-vehicle-per-wave warm loop's bit for bit (with guess_passes <= 0: to the paired mpcqp_fleet_loop's);
@@ -453,7 +453,7 @@ int mpcqp_fleet_loop_warm_carry(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcq
  * device call): info = {kind (MPCQP_LAUNCH_*), QPs or vehicles per wave (1 or 2), workgroups launched,
  * B or V}.  Recorded by mpcqp_solve (plain and mixed builds), mpcqp_solve_warm and the fused-loop calls
  * (mpcqp_fleet_loop, _mixed, _warm, _warm_carry: on `nominal`; mpcqp_swarm_loop's launches record as
- * MPCQP_LAUNCH_LOOP); a call that returns an error or enqueues nothing (B, V or steps 0), and the stepped
+ * MPCQP_LAUNCH_LOOP, mpcqp_swarm_loop_warm's as MPCQP_LAUNCH_LOOP_WARM); a call that returns an error or enqueues nothing (B, V or steps 0), and the stepped
  * fleet and swarm, record nothing.  {MPCQP_LAUNCH_NONE, 0, 0, 0} before any launch and after
  * mpcqp_set_params.  NULL ws or info: MPCQP_E_ARG. */
 #define MPCQP_LAUNCH_NONE 0
@@ -608,6 +608,32 @@ int mpcqp_swarm_run(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, 
  * vehicle as mpcqp_swarm_run to the end, so every fleet and swarm output buffer equals it bit for bit.
  * Parameter blocks without the fused kernel run mpcqp_swarm_run(max_steps, graph). */
 int mpcqp_swarm_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s, void* stream);
+
+/* mpcqp_swarm_loop with every fused-loop launch warm (additive to ABI 9): the same max_replans + 1
+ * rounds of the fused loop with the replan trigger inside, and the same replanning kernels between them.
+ * Inside a launch each vehicle's nominal solve and relaxed retry start from the U of its last accepted
+ * solve, shifted one step down with the last step repeated, under mpcqp_solve_warm's contract (one polish
+ * attempt of at most guess_passes passes; a miss runs the cold solve unchanged).  A vehicle's first step
+ * in a launch is cold; the swarm relaunches a vehicle only after a replan, so a replanned vehicle starts
+ * its new reference cold (the old guess belonged to the reference that is gone).
+ * With guess_passes <= 0 every fleet and swarm output buffer equals mpcqp_swarm_loop's bit for bit, under
+ * any pairing mode.  With a warm start each vehicle's buffers are those of mpcqp_fleet_loop_warm run on
+ * that vehicle alone, segment by segment between its replans, bit for bit (vehicles are independent), and
+ * equal the cold swarm's to rounding only.  The consequence: a replanned vehicle plans from a start that
+ * differs from the cold swarm's in the last bits, and RRT* decisions sit on knife edges (a collision test,
+ * a nearest node), so its new plan may differ from the cold swarm's; each plan is still the reference
+ * planner's plan from where the vehicle stood.
+ * Pairing follows mpcqp_fleet_loop_warm's rule (mpcqp_set_pairing on `nominal`): MPCQP_PAIR_ON runs two
+ * vehicles per wave at N <= 15, every buffer equal to the one-vehicle-per-wave warm swarm's bit for bit;
+ * MPCQP_PAIR_AUTO and MPCQP_PAIR_OFF run one vehicle per wave.  Each launch records as
+ * MPCQP_LAUNCH_LOOP_WARM on `nominal` with its vehicles per wave (mpcqp_launch_info).
+ * Parameter blocks without the fused one-wave loop (N > 32, reproducible, debug_state) return
+ * MPCQP_E_HORIZON, and then nothing is enqueued, written or invalidated: there is no silent cold fallback
+ * (mpcqp_swarm_loop, by contrast, runs mpcqp_swarm_run there).  Null pointers (MPCQP_E_ARG), the swarm
+ * struct's checks and the fleet's are mpcqp_swarm_loop's; V = 0 enqueues nothing.  Out of scope: a guess
+ * kept across a replan or between calls, the stepped swarm, parameter classes. */
+int mpcqp_swarm_loop_warm(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s,
+                          int guess_passes, void* stream);
 
 /*
  * Occupancy inflation: src/maps/inflate.py:18-51 (the fallback

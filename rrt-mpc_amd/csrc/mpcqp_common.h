@@ -575,12 +575,15 @@ struct ServeWarmLaunch {
 };
 typedef void (*serve_warm_t)(hipStream_t, const mpcqp_params&, const ServeWarmLaunch&);
 // One fused-loop launch (device pointers), the loops' counterpart of Launch: k_fleet_loop (tr.pair: two
-// vehicles per wave), k_fleet_loop_mixed (cls != nullptr) and k_fleet_loop_warm read what they need of it.
+// vehicles per wave), k_fleet_loop_mixed (cls != nullptr), k_fleet_loop_warm and k_swarm_loop_warm read what
+// they need of it.
 struct LoopLaunch {
   const mpcqp_params* P;  // {nominal, relaxed}; with cls the 2 K interleaved blocks {nominal[c], relaxed[c]}
   const mpcqp_fleet* f;
   int steps;
-  LoopTrigger tr;  // the mixed and warm loops read only its dispatch order
+  // live in k_fleet_loop and k_swarm_loop_warm (the swarm's calls); the mixed and warm fleet loops read
+  // only its dispatch order, and the carry loop its pairing too
+  LoopTrigger tr;
   const int32_t* cls = nullptr;  // a class per vehicle (V indices) into the K classes
   int K = 0;
   int guess_passes = 0;  // the warm loop's pass limit per attempt
@@ -594,7 +597,8 @@ typedef void (*fleet_loop_t)(hipStream_t, const LoopLaunch&);
 // caller's guess), k_fleet_loop_warm (the fused loop, each step from the one before) and k_serve_warm
 // (the B = 1 server from a caller's guess), k_solve_pair_warm (two QPs per wave from a caller's guess;
 // nullptr above kPairMaxHorizon) and k_fleet_loop_warm_carry (the warm loop with the guess carried across
-// launches; its launcher runs two vehicles per wave where tr.pair).  The object that instantiates a
+// launches; its launcher runs two vehicles per wave where tr.pair) and k_swarm_loop_warm (the warm loop
+// with the swarm's live replan trigger; two per wave where tr.pair).  The object that instantiates a
 // horizon registers it from a namespace-scope initialiser (register_horizons, mpcqp_solve.h); an
 // all-null entry is a horizon not compiled in.
 struct HorizonKernels {
@@ -606,6 +610,7 @@ struct HorizonKernels {
   serve_warm_t serve_warm;
   launcher_t pair_warm;
   fleet_loop_t loop_warm_carry;
+  fleet_loop_t swarm_warm;
 };
 // fills entry N of the table in mpcqp.hip (constant-initialised, so the order of the objects'
 // initialisers does not matter)
@@ -760,7 +765,7 @@ struct mpcqp_ws {
 };
 
 namespace mpcqp {
-// The fused loops (mpcqp_fleet.hip).  fused_loop: the member `which` (loop, loop_mixed, loop_warm) of
+// The fused loops (mpcqp_fleet.hip).  fused_loop: the member `which` (loop, loop_mixed, loop_warm, ...) of
 // the horizon that both workspaces' parameter blocks run, or nullptr (another kernel family, debug
 // mode, not compiled in, or the two differ).  enqueue_fused_loop: one launch of it after the caller's
 // checks -- both builds invalidated, the parameter blocks stored on the stream (L.cls: the two class
@@ -771,7 +776,8 @@ namespace mpcqp {
 fleet_loop_t fused_loop(const mpcqp_ws* nominal, const mpcqp_ws* relaxed, fleet_loop_t HorizonKernels::*which);
 int enqueue_fused_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, fleet_loop_t loop, const char* name, int kind,
                        bool may_pair, LoopLaunch L, hipStream_t s);
-// two QPs (vehicles) per wave for a warm launch (mpcqp_solve_warm, mpcqp_fleet_loop_warm[_carry])?  Only
+// two QPs (vehicles) per wave for a warm launch (mpcqp_solve_warm, mpcqp_fleet_loop_warm[_carry],
+// mpcqp_swarm_loop_warm)?  Only
 // under MPCQP_PAIR_ON and where the paired kernels exist: MPCQP_PAIR_AUTO keeps warm launches at one per
 // wave.  Defined in mpcqp.hip.
 bool use_pairs_warm(const mpcqp_ws* ws);

@@ -2150,6 +2150,9 @@ __global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_solve_pair_warm(
 // every horizon).
 struct FleetCarryWin : FleetWin {};
 
+// SwarmWarmWin: a vehicle of k_swarm_loop_warm: FleetWin exactly; a type of its own for the same reason.
+struct SwarmWarmWin : FleetWin {};
+
 // The carried guess of k_fleet_loop_warm_carry in fleet_loop_body: the V x 2 x N buffer (nullable) and
 // whether a solve of this launch was accepted.  The loops without it carry the empty one (no variable of
 // its own in the body: Guess<false>'s reason).
@@ -2180,7 +2183,12 @@ struct CarryRow<false> {};
 // Carry (k_fleet_loop_warm_carry; with Warm): a RUNNING vehicle's Ug starts from row b of carry.rows
 // instead of NaN, and after the loop the last accepted U goes back there, unshifted (the shift stays at
 // the read inside the step loop) -- only if a solve of this launch was accepted.  Null rows: neither.
-template <int N, bool Pair, bool Warm = false, bool Carry = false>
+// Warm with a live trigger (k_swarm_loop_warm): a vehicle that leaves through to_replan takes no guess
+// with it; paired, the other half of its wave goes on alone, as after a goal.
+// WarmWin: the window type of the warm solves (a type per kernel family, FleetCarryWin's reason); the
+// cold loops never name it.
+template <int N, bool Pair, bool Warm = false, bool Carry = false,
+          class WarmWin = std::conditional_t<Carry, FleetCarryWin, FleetWin>>
 __device__ __forceinline__ void fleet_loop_body(const mpcqp_params* __restrict__ P, const mpcqp_fleet& f, int steps,
                                                 const mpcqp::LoopTrigger& tr, int b, int lane,
                                                 SolveLds<N, Pair>& sm, double* const ls, int guess_passes = 0,
@@ -2248,11 +2256,11 @@ __device__ __forceinline__ void fleet_loop_body(const mpcqp_params* __restrict__
         double up = LN::shl1(Ug);
         asm volatile("" : "+v"(up));  // pinned: the shift runs on every lane, not inside the select below
         const double g = (ln == N - 1 || ln == 2 * N - 1) ? Ug : up;
-        if constexpr (Carry) {
-          st = solve_one<N, FleetCarryWin, Pair, true>(p, b, nullptr, nullptr, nullptr, nullptr, FleetCarryWin{win}, sm,
-                                                       f.u0 + (size_t)relax * V * 2, f.X, nullptr,
-                                                       f.status + (size_t)relax * V, nullptr, nullptr, Ul,
-                                                       Guess<true>{g, guess_passes});
+        if constexpr (!std::is_same_v<WarmWin, FleetWin>) {
+          st = solve_one<N, WarmWin, Pair, true>(p, b, nullptr, nullptr, nullptr, nullptr, WarmWin{win}, sm,
+                                                 f.u0 + (size_t)relax * V * 2, f.X, nullptr,
+                                                 f.status + (size_t)relax * V, nullptr, nullptr, Ul,
+                                                 Guess<true>{g, guess_passes});
         } else {
           st = solve_one<N, FleetWin, Pair, true>(p, b, nullptr, nullptr, nullptr, nullptr, win, sm,
                                                   f.u0 + (size_t)relax * V * 2, f.X, nullptr,
@@ -2425,6 +2433,32 @@ __global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_fleet_loop_warm_
   fleet_loop_body<N, Pair, true, true>(P, f, steps, off, b, lane, sm, ls, guess_passes, CarryRow<true>{U_carry});
 }
 
+// ------------------------------------------------------------------ fused swarm loop, warm started
+// mpcqp_swarm_loop_warm: k_fleet_loop<N, Pair>'s dispatch (slot 2 blockIdx.x + h when paired, tr.order,
+// odd V) and its live replan trigger, around fleet_loop_body's Warm.  Ug starts as NaN in every launch:
+// the swarm relaunches a vehicle only after a replan has given it a new reference, and the old guess
+// belongs to the reference that is gone, so the first step of every vehicle in every launch is cold.
+// A half that leaves the step loop through the trigger is masked off while the other half is still in
+// a warm attempt: every cross-lane read there has its sources in the reader's half (Lanes<true>), and
+// the barrier in front of to_replan is the one k_fleet_loop<N, true> already reaches by one half.
+template <int N, bool Pair = false>
+__global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_swarm_loop_warm(const mpcqp_params* __restrict__ P,
+                                                                              mpcqp_fleet f, int steps,
+                                                                              mpcqp::LoopTrigger tr,
+                                                                              int guess_passes) {
+  static_assert(!Pair || 2 * N <= 30, "two vehicles per wave need n = 2N <= 30");
+  __shared__ SolveLds<N, Pair> smv[Pair ? 2 : 1];
+  __shared__ double lsv[Pair ? 12 : 6];  // loop state: x[4], u_prev[2] (per half)
+  const int h = Pair ? (int)(threadIdx.x >> 5) : 0;
+  SolveLds<N, Pair>& sm = smv[h];
+  double* const ls = lsv + 6 * h;
+  const int slot = Pair ? 2 * (int)blockIdx.x + h : (int)blockIdx.x;  // pair: may be V (odd V)
+  const int b = (tr.order && slot < f.vehicles) ? tr.order[slot] : slot;
+  const int lane = Pair ? (int)(threadIdx.x & 31) : (int)threadIdx.x;
+  if (b < 0 || b >= f.vehicles) return;
+  fleet_loop_body<N, Pair, true, false, SwarmWarmWin>(P, f, steps, tr, b, lane, sm, ls, guess_passes);
+}
+
 // ------------------------------------------------------------------ B = 1 server
 // One resident wave serving the sequential closed loop of TrajectoryTracker.track: it waits for the
 // host to raise box->req (system-scope loads of pinned host memory, s_sleep between polls), solves the
@@ -2580,6 +2614,20 @@ void launch_fleet_loop_warm_carry(hipStream_t s, const LoopLaunch& L) {
   hipLaunchKernelGGL((k_fleet_loop_warm_carry<N, false>), dim3(f.vehicles), dim3(kWave), 0, s, L.P, f, L.steps,
                      L.guess_passes, L.tr.order, L.carry);
 }
+// the warm loop with the swarm's live trigger (L.tr); L.tr.pair: two vehicles per wave
+template <int N>
+void launch_swarm_loop_warm(hipStream_t s, const LoopLaunch& L) {
+  const mpcqp_fleet& f = *L.f;
+  if constexpr (N <= kPairMaxHorizon) {
+    if (L.tr.pair) {
+      hipLaunchKernelGGL((k_swarm_loop_warm<N, true>), dim3((f.vehicles + 1) / 2), dim3(kWave), 0, s, L.P, f, L.steps,
+                         L.tr, L.guess_passes);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((k_swarm_loop_warm<N, false>), dim3(f.vehicles), dim3(kWave), 0, s, L.P, f, L.steps, L.tr,
+                     L.guess_passes);
+}
 // two QPs per wave from a caller's guess (N <= kPairMaxHorizon)
 template <int N>
 void launch_solve_pair_warm(hipStream_t s, const Launch& L) {
@@ -2602,7 +2650,7 @@ template <int LO, int HI>
 int register_horizons() {
   HorizonKernels k{&launch_solve<LO>, &launch_solve_mixed<LO>, nullptr, &launch_serve<LO>, &launch_fleet_loop<LO>,
                    &launch_fleet_loop_mixed<LO>, &launch_solve_warm<LO>, &launch_fleet_loop_warm<LO>,
-                   &launch_serve_warm<LO>, nullptr, &launch_fleet_loop_warm_carry<LO>};
+                   &launch_serve_warm<LO>, nullptr, &launch_fleet_loop_warm_carry<LO>, &launch_swarm_loop_warm<LO>};
   if constexpr (LO <= kPairMaxHorizon) {
     k.pair = &launch_solve_pair<LO>;
     k.pair_warm = &launch_solve_pair_warm<LO>;

@@ -20,7 +20,8 @@
 // costs a handful of empty launches; mpcqp_swarm_run replays the whole step as a hipGraph.
 // mpcqp_swarm_loop runs the same thing as max_replans + 1 launches of the fused fleet loop
 // (k_fleet_loop with the trigger: each vehicle steps until it triggers or ends) with the replanning
-// kernels in between -- no per-step launches.
+// kernels in between -- no per-step launches.  mpcqp_swarm_loop_warm is the same rounds with
+// k_swarm_loop_warm: each vehicle's solves start from its step before, cold at the first step of a launch.
 #include "mpcqp_build.h"
 #include "mpcqp_plan.h"
 #include "mpcqp_refbuild.h"
@@ -264,26 +265,48 @@ int mpcqp_swarm_step(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f,
   return enqueue_replan(f, s, st);
 }
 
-int mpcqp_swarm_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s, void* stream) {
+// mpcqp_swarm_loop (warm == false) and mpcqp_swarm_loop_warm after the swarm's and the fleet's checks:
+// max_replans + 1 rounds of the fused loop with the trigger inside -- every vehicle runs until it
+// triggers or ends, the flagged ones are replanned; a vehicle's r-th trigger comes in round r - 1, so
+// the last round triggers none.  Cold, a parameter block without the fused loop runs the stepped swarm
+// to the end; warm, it is refused before anything is enqueued or invalidated.
+static int swarm_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s, bool warm,
+                      int guess_passes, void* stream) {
   int rc = check_swarm(f, s);
   if (rc) return rc;
   rc = mpcqp_fleet_loop(nominal, relaxed, f, 0, stream);  // the fleet's checks (no work at 0 steps)
   if (rc) return rc;
+  const mpcqp::fleet_loop_t loop = mpcqp::fused_loop(
+      nominal, relaxed, warm ? &mpcqp::HorizonKernels::swarm_warm : &mpcqp::HorizonKernels::loop);
+  if (warm && !loop)
+    return fail(MPCQP_E_HORIZON, "mpcqp_swarm_loop_warm runs the fused one-wave loop only (N <= 32, fast mode, no "
+                                 "debug_state): the stepped swarm takes no guess");
   if (f->vehicles == 0) return MPCQP_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (s->max_replans > 0 && (rc = set_replan_attrs(s)) != MPCQP_OK) return rc;
-  // max_replans + 1 rounds: every vehicle runs until it triggers or ends, the flagged ones are
-  // replanned; a vehicle's r-th trigger comes in round r - 1, so the last round triggers none
-  const mpcqp::fleet_loop_t loop = mpcqp::fused_loop(nominal, relaxed, &mpcqp::HorizonKernels::loop);
   if (!loop)  // mid / long horizons, reproducible or debug mode: the stepped swarm to the end
     return mpcqp_swarm_run(nominal, relaxed, f, s, f->max_steps, 1, stream);
-  const mpcqp::LoopTrigger tr{s->replan_distance, s->max_replans, s->replans, s->start_goal};
+  mpcqp::LoopLaunch L{nullptr, f, f->max_steps, {s->replan_distance, s->max_replans, s->replans, s->start_goal}};
+  if (warm) {
+    L.guess_passes = guess_passes;
+    L.tr.pair = mpcqp::use_pairs_warm(nominal);
+  }
   for (int r = 0; r <= s->max_replans; ++r) {
-    rc = mpcqp::enqueue_fused_loop(nominal, relaxed, loop, "k_fleet_loop", MPCQP_LAUNCH_LOOP, true, {nullptr, f, f->max_steps, tr}, st);
+    rc = mpcqp::enqueue_fused_loop(nominal, relaxed, loop, warm ? "k_swarm_loop_warm" : "k_fleet_loop",
+                                   warm ? MPCQP_LAUNCH_LOOP_WARM : MPCQP_LAUNCH_LOOP, !warm, L, st);
     if (rc) return rc;
     if (r < s->max_replans && (rc = enqueue_replan(f, s, st, false)) != MPCQP_OK) return rc;
   }
   return MPCQP_OK;
+}
+
+int mpcqp_swarm_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s, void* stream) {
+  return swarm_loop(nominal, relaxed, f, s, false, 0, stream);
+}
+
+int mpcqp_swarm_loop_warm(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s,
+                          int guess_passes, void* stream) {
+  return swarm_loop(nominal, relaxed, f, s, true, guess_passes, stream);
 }
 
 int mpcqp_swarm_run(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s, int steps,

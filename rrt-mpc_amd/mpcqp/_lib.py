@@ -337,6 +337,8 @@ _SYMBOLS = {
     "mpcqp_stage_guess": ([ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)], ctypes.c_int),
     "mpcqp_solve_staged_warm": ([ctypes.c_void_p, ctypes.c_int], ctypes.c_int),
     "mpcqp_solve_served_warm": ([ctypes.c_void_p, ctypes.c_int], ctypes.c_int),
+    "mpcqp_swarm_loop_warm": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MpcqpFleet),
+                               ctypes.POINTER(MpcqpSwarm), ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
 }
 
 

@@ -15,7 +15,10 @@ on the GPU with a per-step replan trigger.
                0.  At most ``max_replans`` per vehicle.  The whole step is one hipGraph replay; the
                host only polls every ``check_every`` steps whether any vehicle still runs.  With
                ``fused=True``: ``mpcqp_swarm_loop``, the fused fleet loop with the trigger inside
-               (max_replans + 1 launches, the replanning kernels between them).
+               (max_replans + 1 launches, the replanning kernels between them).  With
+               ``warm_start=True`` as well: ``mpcqp_swarm_loop_warm``, the same launches with each
+               vehicle's solves started from its step before (cold at the first step of a launch, so
+               a replanned vehicle starts its new reference cold).
 Every vehicle between replans follows the reference's single-vehicle loop exactly.
 """
 from __future__ import annotations
@@ -56,10 +59,22 @@ class SwarmResult:
 
 
 class Swarm:
+    warm_start = False
+    guess_passes = _lib.DEFAULT_GUESS_PASSES
+
     def __init__(self, occupancy: np.ndarray, mpc, planner: PlannerParameters, *, map_resolution: float,
                  max_vehicles: int, max_ref_len: int = 512, device=None, replan_distance: float = 15.0,
                  max_replans: int = 2, path_cap: int = 6144, use_graph: bool = True, fused: bool = False,
-                 **settings) -> None:
+                 warm_start: bool = False, guess_passes: Optional[int] = None, **settings) -> None:
+        # warm start (mpcqp_swarm_loop_warm): opt-in, the fused swarm only.  Results equal the cold swarm's
+        # to rounding, so a replanned vehicle's new plan may differ from the cold swarm's (RRT* decisions
+        # sit on knife edges); guess_passes <= 0 is the cold swarm bit for bit.
+        if warm_start and not fused:
+            raise ValueError("warm_start needs fused=True: only the fused swarm loop carries a guess from step to step")
+        if guess_passes is not None and not warm_start:
+            raise ValueError("guess_passes needs warm_start=True")
+        self.warm_start = bool(warm_start)
+        self.guess_passes = _lib.DEFAULT_GUESS_PASSES if guess_passes is None else int(guess_passes)
         # path_cap: smoothed points a replan may produce.  The default is the most that the device
         # reference builder stages (kRefCap, csrc/mpcqp_swarm.hip), so a replanned path is never cut
         # shorter than a reference could be built from; capacity failures are reported apart from
@@ -163,9 +178,10 @@ class Swarm:
         stream = torch.cuda.current_stream(self.device)
         done = 0
         if self.fused and V:
-            _lib.check(self._L.mpcqp_swarm_loop(self.fleet._nominal._ws, self.fleet._relaxed._ws,
-                                                ctypes.byref(self.fleet._fleet), ctypes.byref(sw),
-                                                ctypes.c_void_p(stream.cuda_stream)), "mpcqp_swarm_loop")
+            call, args = ("mpcqp_swarm_loop_warm", (self.guess_passes,)) if self.warm_start else ("mpcqp_swarm_loop", ())
+            _lib.check(getattr(self._L, call)(self.fleet._nominal._ws, self.fleet._relaxed._ws,
+                                              ctypes.byref(self.fleet._fleet), ctypes.byref(sw), *args,
+                                              ctypes.c_void_p(stream.cuda_stream)), call)
             done = total
         while done < total and V:
             k = min(check_every, total - done)

@@ -6,6 +6,10 @@ reference algorithm restated in Python on one host core) and the inflation kerne
 
     python tools/swarm_bench.py [--vehicles 100 1024] [--steps 300]
 
+The warm start (Swarm(fused=True, warm_start=True)) against the cold fused swarm, interleaved:
+
+    python tools/swarm_bench.py --warm [--guess-passes 8] [--reps 5] [--pairing auto|on|off]
+
 Multi-GPU (BASELINE config 5 on 8 GPUs): vehicles sharded over ranks (mpcqp.pipeline.swarm
 .run_swarm_sharded), one process per GPU, the per-vehicle results gathered at the end:
 
@@ -96,6 +100,68 @@ def distributed(a) -> None:
     dist.destroy_process_group()
 
 
+def warm_bench(a) -> None:
+    """The cold fused swarm (mpcqp_swarm_loop) against the warm-started one (mpcqp_swarm_loop_warm) at each
+    --guess-passes value, on the same starts, goals and seeds, under --pairing: whole Swarm.run calls, the
+    legs alternating within every repeat in one process with the order rotating from repeat to repeat;
+    repeat 0 warms up.  Per leg: medians with min and max of track_replan_s (the fused-loop launches and the
+    replanning between them, up to a synchronise) and of the end-to-end run (planning and references
+    included), vehicle-steps, replans, and whether steps, phases and replan steps agree with the cold leg."""
+    import torch
+
+    from mpcqp.config import MPCConfig
+    from mpcqp.pipeline.swarm import Swarm
+    from mpcqp.planning.rrt_star import default_planner_parameters
+
+    occ = np.load(ROOT / "rrt-mpc_amd" / "mpcqp" / "data" / "default_plan.npz")["occupancy"]
+    prm = default_planner_parameters()
+    out = {"metric": "Swarm.run seconds, cold and warm legs interleaved", "horizon": 15, "sim_steps": a.steps,
+           "replan_distance": a.replan_distance, "max_replans": a.max_replans, "pairing": a.pairing, "reps": a.reps,
+           "runs": []}
+    for V in a.vehicles:
+        starts, goals = pairs(occ, V, 5)
+        kw = dict(map_resolution=0.8, max_vehicles=V, device="cuda:0", replan_distance=a.replan_distance,
+                  max_replans=a.max_replans, fused=True, pairing=a.pairing)
+        mpc = MPCConfig(horizon=15, sim_steps=a.steps)
+        legs = {"cold": Swarm(occ, mpc, prm, **kw)}
+        for gp in a.guess_passes:
+            legs[f"warm:{gp}"] = Swarm(occ, mpc, prm, warm_start=True, guess_passes=gp, **kw)
+        names = list(legs)
+        times = {k: {"track_replan_s": [], "end_to_end_s": []} for k in names}
+        res = {}
+        for r in range(a.reps + 1):  # repeat 0 warms up
+            for k in names[r % len(names):] + names[:r % len(names)]:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                res[k] = legs[k].run(starts, goals, seeds=np.arange(V))
+                torch.cuda.synchronize()
+                if r:
+                    times[k]["end_to_end_s"].append(time.perf_counter() - t0)
+                    times[k]["track_replan_s"].append(res[k].timings["track_replan_s"])
+        cold = res["cold"]
+        run = {"vehicles": V, "planned": int(cold.planned.sum())}
+        for k in names:
+            rk = res[k]
+            info = legs[k].fleet._nominal.launch_info()
+            run[k] = {"vehicle_steps": int(rk.steps.sum()), "goal_reached": int((rk.phase == 1).sum()),
+                      "replans": int(rk.replans.sum()), "replans_with_new_plan": int((rk.replan_steps > 0).sum()),
+                      "vehicles_replanned": int((rk.replans > 0).sum()), "launch": info["name"],
+                      "per_wave": info["per_wave"],
+                      "same_steps": bool(np.array_equal(rk.steps, cold.steps)),
+                      "same_phases": bool(np.array_equal(rk.phase, cold.phase)),
+                      "same_replan_steps": bool(np.array_equal(rk.replan_steps, cold.replan_steps)),
+                      "vehicles_with_other_steps": int((rk.steps != cold.steps).sum())}
+            for what, ts in times[k].items():
+                med = float(np.median(ts))
+                run[k][what] = {"median": med, "min": min(ts), "max": max(ts), "all": ts,
+                                "over_cold": med / float(np.median(times["cold"][what]))}
+        out["runs"].append(run)
+        for sw in legs.values():
+            sw.fleet.close()
+        print(json.dumps(run), flush=True)
+    print(json.dumps(out))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--vehicles", type=int, nargs="+", default=[100, 1024])
@@ -107,9 +173,25 @@ def main() -> None:
     ap.add_argument("--fused", action="store_true",
                     help="mpcqp_swarm_loop: the fused fleet loop with the trigger inside (max_replans + 1 launches)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"])
+    ap.add_argument("--warm", action="store_true",
+                    help="the cold fused swarm against the warm-started one (mpcqp_swarm_loop_warm), interleaved")
+    ap.add_argument("--guess-passes", type=int, nargs="+", default=None,
+                    help="with --warm: the attempt's pass limits to compare (default: the library's)")
+    ap.add_argument("--reps", type=int, default=5, help="with --warm: timed repeats per leg, after a warm-up repeat")
+    ap.add_argument("--pairing", default="auto", choices=["auto", "on", "off"],
+                    help="with --warm: two vehicles per wave (mpcqp_set_pairing); a warm launch pairs under \"on\" only")
     a = ap.parse_args()
     if a.distributed:
         distributed(a)
+        return
+    if a.warm:
+        if a.reps < 1:
+            ap.error("--reps must be >= 1")
+        if a.guess_passes is None:
+            from mpcqp import _lib
+
+            a.guess_passes = [_lib.DEFAULT_GUESS_PASSES]
+        warm_bench(a)
         return
     import torch
 
