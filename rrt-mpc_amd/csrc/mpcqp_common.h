@@ -599,8 +599,8 @@ typedef void (*fleet_loop_t)(hipStream_t, const LoopLaunch&);
 // nullptr above kPairMaxHorizon) and k_fleet_loop_warm_carry (the warm loop with the guess carried across
 // launches; its launcher runs two vehicles per wave where tr.pair) and k_swarm_loop_warm (the warm loop
 // with the swarm's live replan trigger; two per wave where tr.pair).  The object that instantiates a
-// horizon registers it from a namespace-scope initialiser (register_horizons, mpcqp_solve.h); an
-// all-null entry is a horizon not compiled in.
+// horizon registers it from a namespace-scope initialiser (register_horizons, mpcqp_solve.h: member by
+// member, since five of them share one type); an all-null entry is a horizon not compiled in.
 struct HorizonKernels {
   launcher_t solve, mixed, pair;
   serve_t serve;

@@ -2648,9 +2648,17 @@ void launch_solve_pair(hipStream_t s, const Launch& L) {
 // instantiates the kernels).  A new per-horizon entry point: a member of HorizonKernels, and here.
 template <int LO, int HI>
 int register_horizons() {
-  HorizonKernels k{&launch_solve<LO>, &launch_solve_mixed<LO>, nullptr, &launch_serve<LO>, &launch_fleet_loop<LO>,
-                   &launch_fleet_loop_mixed<LO>, &launch_solve_warm<LO>, &launch_fleet_loop_warm<LO>,
-                   &launch_serve_warm<LO>, nullptr, &launch_fleet_loop_warm_carry<LO>, &launch_swarm_loop_warm<LO>};
+  HorizonKernels k{};  // by member name: five members share fleet_loop_t, and a swapped pair would compile
+  k.solve = &launch_solve<LO>;
+  k.mixed = &launch_solve_mixed<LO>;
+  k.serve = &launch_serve<LO>;
+  k.loop = &launch_fleet_loop<LO>;
+  k.loop_mixed = &launch_fleet_loop_mixed<LO>;
+  k.warm = &launch_solve_warm<LO>;
+  k.loop_warm = &launch_fleet_loop_warm<LO>;
+  k.serve_warm = &launch_serve_warm<LO>;
+  k.loop_warm_carry = &launch_fleet_loop_warm_carry<LO>;
+  k.swarm_warm = &launch_swarm_loop_warm<LO>;
   if constexpr (LO <= kPairMaxHorizon) {
     k.pair = &launch_solve_pair<LO>;
     k.pair_warm = &launch_solve_pair_warm<LO>;

@@ -27,7 +27,8 @@ from pathlib import Path
 HERE = Path(__file__).resolve().parents[1]
 BEGIN = re.compile(r"; -- Begin function (\S+)")
 END = re.compile(r"; -- End function")
-LABEL = re.compile(r"\.(LBB|Ltmp|Lfunc_end|Lfunc_begin|LJTI)\d+(?:_\d+)*")
+# Lpost_getpc: the label of a relaxed (long) branch, numbered through the whole file
+LABEL = re.compile(r"\.(LBB|Ltmp|Lfunc_end|Lfunc_begin|LJTI|Lpost_getpc)\d+(?:_\d+)*")
 
 
 def _jobs(tree: Path, out: Path) -> dict[str, list[str]]:
