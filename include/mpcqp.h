@@ -305,6 +305,8 @@ int mpcqp_set_pairing(mpcqp_ws* ws, int mode);
  *
  * The one fleet call that reads the tables is mpcqp_fleet_loop_mixed (below, after mpcqp_fleet_loop): the
  * fused closed loop with a class per vehicle.  Fused loop only, never paired; the swarm is unchanged.
+ * The swarm calls that read the tables are calls of their own: mpcqp_swarm_loop_mixed and
+ * mpcqp_swarm_loop_mixed_warm (below, after mpcqp_swarm_loop_warm).
  */
 #define MPCQP_BAD_CLASS (-11)   /* per-QP status: class index outside [0, K) */
 
@@ -406,7 +408,8 @@ int mpcqp_fleet_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f,
  * wave would need two blocks).  The replan trigger is off and the swarm is unchanged (its replanning
  * builds references with one dt).  Out of scope: mixed mpcqp_fleet_step / mpcqp_fleet_run (and with
  * them horizons above 32, reproducible mode and debug_state: the stepped path would need a mask and a
- * model input in the three mixed solve kernels), the swarm, and the B = 1 paths. */
+ * model input in the three mixed solve kernels), the swarm, and the B = 1 paths.  (A mixed fleet that
+ * replans, and the warm mixed loop, are mpcqp_swarm_loop_mixed / mpcqp_swarm_loop_mixed_warm.) */
 int mpcqp_fleet_loop_mixed(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const int32_t* cls, int steps,
                            void* stream);
 
@@ -453,7 +456,8 @@ int mpcqp_fleet_loop_warm_carry(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcq
  * device call): info = {kind (MPCQP_LAUNCH_*), QPs or vehicles per wave (1 or 2), workgroups launched,
  * B or V}.  Recorded by mpcqp_solve (plain and mixed builds), mpcqp_solve_warm and the fused-loop calls
  * (mpcqp_fleet_loop, _mixed, _warm, _warm_carry: on `nominal`; mpcqp_swarm_loop's launches record as
- * MPCQP_LAUNCH_LOOP, mpcqp_swarm_loop_warm's as MPCQP_LAUNCH_LOOP_WARM); a call that returns an error or enqueues nothing (B, V or steps 0), and the stepped
+ * MPCQP_LAUNCH_LOOP, mpcqp_swarm_loop_warm's as MPCQP_LAUNCH_LOOP_WARM, mpcqp_swarm_loop_mixed's as
+ * MPCQP_LAUNCH_LOOP_MIXED, mpcqp_swarm_loop_mixed_warm's as MPCQP_LAUNCH_LOOP_MIXED_WARM); a call that returns an error or enqueues nothing (B, V or steps 0), and the stepped
  * fleet and swarm, record nothing.  {MPCQP_LAUNCH_NONE, 0, 0, 0} before any launch and after
  * mpcqp_set_params.  NULL ws or info: MPCQP_E_ARG. */
 #define MPCQP_LAUNCH_NONE 0
@@ -464,6 +468,7 @@ int mpcqp_fleet_loop_warm_carry(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcq
 #define MPCQP_LAUNCH_LOOP_MIXED 5
 #define MPCQP_LAUNCH_LOOP_WARM 6
 #define MPCQP_LAUNCH_LOOP_WARM_CARRY 7
+#define MPCQP_LAUNCH_LOOP_MIXED_WARM 8 /* mpcqp_swarm_loop_mixed_warm (the cold call records LOOP_MIXED) */
 int mpcqp_launch_info(const mpcqp_ws* ws, int32_t info[4]);
 
 /*
@@ -634,6 +639,50 @@ int mpcqp_swarm_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f,
  * kept across a replan or between calls, the stepped swarm, parameter classes. */
 int mpcqp_swarm_loop_warm(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s,
                           int guess_passes, void* stream);
+
+/* mpcqp_swarm_loop for a heterogeneous swarm (additive to ABI 9): mixed fleets that replan.  The same
+ * max_replans + 1 rounds of the fused loop with the replan trigger inside and the same replanning kernels
+ * between them; vehicle v steps under block cls[v] of `nominal`'s class table and retries under block
+ * cls[v] of `relaxed`'s table (mpcqp_set_classes on both), and its plant uses dt and wheelbase_px of its
+ * nominal block.  cls: V int32 in device memory, valid until the last launch has run (stream order).
+ * A swarm has one dt and one reference speed: the replanning builds every new reference with s->dt, s->desired_speed and
+ * s->horizon, so every block of both tables must have dt == s->dt (MPCQP_E_ARG otherwise; the message
+ * names the class).  Everything else may differ per class, as for mpcqp_fleet_loop_mixed.
+ * Every fleet and swarm buffer of vehicle v, and its reference rows after its replans, equal, bit for
+ * bit, those of mpcqp_swarm_loop (one vehicle per wave) for a homogeneous swarm under its class's two
+ * blocks: vehicles are independent, and each replans from its own rng_table row.  With
+ * s->max_replans == 0 (a dead trigger) the buffers are those of mpcqp_fleet_loop_mixed(..., steps =
+ * f->max_steps) bit for bit.
+ * A vehicle whose cls[v] lies outside [0, K) never indexes a table.  RUNNING, its phase becomes
+ * MPCQP_FLEET_ABORTED, status[v] MPCQP_BAD_CLASS, mask[v] and mask[V + v] 0 and nothing else of it is
+ * written; ABORTED, nothing of it is written.  In both cases it is not handed to the replanner: its
+ * replans[v], start_goal row, replan_step row and reference rows stay as they were, and the other vehicles
+ * run as usual.  The class is read for RUNNING vehicles and for ABORTED ones with replans left; a vehicle
+ * in any other phase is skipped before it.
+ * Errors, each before anything is enqueued, written or invalidated: NULL cls, workspaces, fleet or swarm
+ * MPCQP_E_ARG; parameter blocks without the fused one-wave loop (N > 32, reproducible, debug_state)
+ * MPCQP_E_HORIZON -- there is no stepped fallback, the stepped swarm has no classes; no class table on
+ * `nominal`, none on `relaxed`, or two tables of different K MPCQP_E_STATE (the message names the
+ * workspace).  The swarm struct's checks and the fleet's are mpcqp_swarm_loop's; V = 0 enqueues nothing.
+ * Never paired: one vehicle per wave whatever mpcqp_set_pairing says (two vehicles of different classes per
+ * wave would need two blocks).  Each launch records as MPCQP_LAUNCH_LOOP_MIXED on `nominal`, one vehicle
+ * per wave (mpcqp_launch_info).  Out of scope: classes in the stepped swarm (mpcqp_swarm_step / _run), a
+ * dt or reference speed per class. */
+int mpcqp_swarm_loop_mixed(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s,
+                           const int32_t* cls, void* stream);
+
+/* mpcqp_swarm_loop_mixed with every fused-loop launch warm (additive to ABI 9): inside a launch each
+ * vehicle's two solves start from the U of its last accepted solve under mpcqp_swarm_loop_warm's rules (a
+ * vehicle's first step in a launch is cold, so a replanned vehicle starts its new reference cold).  Every
+ * buffer of vehicle v equals, bit for bit, that of mpcqp_swarm_loop_warm (one vehicle per wave) for a
+ * homogeneous swarm under its class's two blocks; with guess_passes <= 0 the buffers are
+ * mpcqp_swarm_loop_mixed's bit for bit.  With s->max_replans == 0 this is the warm mixed fleet loop: each
+ * vehicle's buffers are mpcqp_fleet_loop_warm's under its class's blocks.  One dt, the bad-class rule,
+ * the errors (MPCQP_E_ARG, MPCQP_E_HORIZON, MPCQP_E_STATE, nothing written) and "never paired" are
+ * mpcqp_swarm_loop_mixed's.  Each launch records as MPCQP_LAUNCH_LOOP_MIXED_WARM on `nominal`.  Out of scope:
+ * a guess kept across a replan or between calls, two vehicles of different classes per wave. */
+int mpcqp_swarm_loop_mixed_warm(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s,
+                                const int32_t* cls, int guess_passes, void* stream);
 
 /*
  * Occupancy inflation: src/maps/inflate.py:18-51 (the fallback

@@ -307,6 +307,7 @@ int mpcqp_set_classes(mpcqp_ws* ws, int K, const mpcqp_params* blocks) {
     }
     ws->dclasses = table;
     ws->n_classes = K;
+    ws->hclasses.assign(blocks, blocks + K);
     ws->invalidate();
   } else if (table) {
     (void)hipFree(table);

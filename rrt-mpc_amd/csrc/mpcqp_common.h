@@ -14,6 +14,7 @@
 #include <string>
 #include <type_traits>
 #include <utility>
+#include <vector>
 
 #include "../../include/mpcqp.h"
 
@@ -581,8 +582,8 @@ struct LoopLaunch {
   const mpcqp_params* P;  // {nominal, relaxed}; with cls the 2 K interleaved blocks {nominal[c], relaxed[c]}
   const mpcqp_fleet* f;
   int steps;
-  // live in k_fleet_loop and k_swarm_loop_warm (the swarm's calls); the mixed and warm fleet loops read
-  // only its dispatch order, and the carry loop its pairing too
+  // live in k_fleet_loop, k_swarm_loop_warm and k_swarm_loop_mixed[_warm] (the swarm's calls); the mixed and
+  // warm fleet loops read only its dispatch order, and the carry loop its pairing too
   LoopTrigger tr;
   const int32_t* cls = nullptr;  // a class per vehicle (V indices) into the K classes
   int K = 0;
@@ -598,9 +599,10 @@ typedef void (*fleet_loop_t)(hipStream_t, const LoopLaunch&);
 // (the B = 1 server from a caller's guess), k_solve_pair_warm (two QPs per wave from a caller's guess;
 // nullptr above kPairMaxHorizon) and k_fleet_loop_warm_carry (the warm loop with the guess carried across
 // launches; its launcher runs two vehicles per wave where tr.pair) and k_swarm_loop_warm (the warm loop
-// with the swarm's live replan trigger; two per wave where tr.pair).  The object that instantiates a
+// with the swarm's live replan trigger; two per wave where tr.pair), k_swarm_loop_mixed and
+// k_swarm_loop_mixed_warm (the swarm's cold and warm loops with a class per vehicle; never paired).  The object that instantiates a
 // horizon registers it from a namespace-scope initialiser (register_horizons, mpcqp_solve.h: member by
-// member, since five of them share one type); an all-null entry is a horizon not compiled in.
+// member, since seven of them share one type); an all-null entry is a horizon not compiled in.
 struct HorizonKernels {
   launcher_t solve, mixed, pair;
   serve_t serve;
@@ -611,6 +613,7 @@ struct HorizonKernels {
   launcher_t pair_warm;
   fleet_loop_t loop_warm_carry;
   fleet_loop_t swarm_warm;
+  fleet_loop_t swarm_mixed, swarm_mixed_warm;
 };
 // fills entry N of the table in mpcqp.hip (constant-initialised, so the order of the objects'
 // initialisers does not matter)
@@ -748,6 +751,8 @@ struct mpcqp_ws {
   // per-QP parameter classes (mpcqp_set_classes): the device table of n_classes blocks
   mpcqp_params* dclasses = nullptr;
   int n_classes = 0;
+  // the table's blocks on the host (mpcqp_swarm_loop_mixed checks every class's dt against the swarm's)
+  std::vector<mpcqp_params> hclasses;
   // mpcqp_fleet_loop_mixed (on the nominal workspace): 2 K blocks {nominal[c], relaxed[c]} for
   // dloop_cap classes, filled from the two class tables by a kernel on the launch stream at every call
   mpcqp_params* dloop_classes = nullptr;
@@ -776,6 +781,12 @@ namespace mpcqp {
 fleet_loop_t fused_loop(const mpcqp_ws* nominal, const mpcqp_ws* relaxed, fleet_loop_t HorizonKernels::*which);
 int enqueue_fused_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, fleet_loop_t loop, const char* name, int kind,
                        bool may_pair, LoopLaunch L, hipStream_t s);
+// The mixed loops' class tables (mpcqp_fleet_loop_mixed, mpcqp_swarm_loop_mixed[_warm]; mpcqp_fleet.hip).
+// check_loop_classes: MPCQP_E_STATE, the message under `who`, unless both workspaces hold a table of the
+// same K >= 1; writes nothing.  grow_loop_classes: nominal->dloop_classes for nominal->n_classes classes,
+// allocated outside any capture (MPCQP_E_STATE inside one).
+int check_loop_classes(const mpcqp_ws* nominal, const mpcqp_ws* relaxed, const char* who);
+int grow_loop_classes(mpcqp_ws* nominal, hipStream_t s);
 // two QPs (vehicles) per wave for a warm launch (mpcqp_solve_warm, mpcqp_fleet_loop_warm[_carry],
 // mpcqp_swarm_loop_warm)?  Only
 // under MPCQP_PAIR_ON and where the paired kernels exist: MPCQP_PAIR_AUTO keeps warm launches at one per

@@ -275,6 +275,38 @@ fleet_loop_t fused_loop(const mpcqp_ws* nominal, const mpcqp_ws* relaxed, fleet_
   return kn && kr && kn->*which == kr->*which ? kn->*which : nullptr;
 }
 
+int check_loop_classes(const mpcqp_ws* nominal, const mpcqp_ws* relaxed, const char* who) {
+  const std::string w(who);
+  const int K = nominal->n_classes;
+  if (K < 1 || !nominal->dclasses)
+    return fail(MPCQP_E_STATE, w + ": the nominal workspace holds no class table (mpcqp_set_classes)");
+  if (relaxed->n_classes < 1 || !relaxed->dclasses)
+    return fail(MPCQP_E_STATE, w + ": the relaxed workspace holds no class table (mpcqp_set_classes)");
+  if (relaxed->n_classes != K)
+    return fail(MPCQP_E_STATE, w + ": the relaxed workspace holds " + std::to_string(relaxed->n_classes) +
+                                   " classes, the nominal workspace " + std::to_string(K));
+  return MPCQP_OK;
+}
+
+int grow_loop_classes(mpcqp_ws* nominal, hipStream_t s) {
+  const int K = nominal->n_classes;
+  if (nominal->dloop_cap >= K) return MPCQP_OK;
+  // the interleaved table grows outside any capture (hipFree waits for its readers)
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (s && hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    return fail(MPCQP_E_STATE, "the mixed loop's class table is allocated at its first use, which cannot be inside "
+                               "a stream capture: run the call once uncaptured first");
+  const DeviceGuard dev(nominal->device);
+  hipError_t e = dev.err;
+  mpcqp_params* table = nullptr;
+  if (e == hipSuccess) e = hipMalloc(&table, 2 * sizeof(mpcqp_params) * (size_t)K);
+  if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("hipMalloc (mixed loop classes): ") + hipGetErrorString(e));
+  if (nominal->dloop_classes) (void)hipFree(nominal->dloop_classes);
+  nominal->dloop_classes = table;
+  nominal->dloop_cap = K;
+  return MPCQP_OK;
+}
+
 int enqueue_fused_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, fleet_loop_t loop, const char* name, int kind,
                        bool may_pair, LoopLaunch L, hipStream_t s) {
   nominal->invalidate();  // as mpcqp_fleet_step: a later mpcqp_solve needs its own build
@@ -326,33 +358,13 @@ int mpcqp_fleet_loop_mixed(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fle
   if (!loop)
     return fail(MPCQP_E_HORIZON, "mpcqp_fleet_loop_mixed runs the fused one-wave loop only (N <= 32, fast mode, no "
                                  "debug_state): the stepped fleet has no per-vehicle classes");
-  const int K = nominal->n_classes;
-  if (K < 1 || !nominal->dclasses)
-    return fail(MPCQP_E_STATE, "mpcqp_fleet_loop_mixed: the nominal workspace holds no class table (mpcqp_set_classes)");
-  if (relaxed->n_classes < 1 || !relaxed->dclasses)
-    return fail(MPCQP_E_STATE, "mpcqp_fleet_loop_mixed: the relaxed workspace holds no class table (mpcqp_set_classes)");
-  if (relaxed->n_classes != K)
-    return fail(MPCQP_E_STATE, "mpcqp_fleet_loop_mixed: the relaxed workspace holds " + std::to_string(relaxed->n_classes) +
-                                   " classes, the nominal workspace " + std::to_string(K));
+  if ((rc = mpcqp::check_loop_classes(nominal, relaxed, "mpcqp_fleet_loop_mixed")) != MPCQP_OK) return rc;
   if (f->vehicles == 0 || steps == 0) return MPCQP_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (nominal->dloop_cap < K) {  // the interleaved table grows outside any capture (hipFree waits for its readers)
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (s && hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-      return fail(MPCQP_E_STATE, "the mixed loop's class table is allocated at its first use, which cannot be inside "
-                                 "a stream capture: run the call once uncaptured first");
-    const mpcqp::DeviceGuard dev(nominal->device);
-    hipError_t e = dev.err;
-    mpcqp_params* table = nullptr;
-    if (e == hipSuccess) e = hipMalloc(&table, 2 * sizeof(mpcqp_params) * (size_t)K);
-    if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("hipMalloc (mixed loop classes): ") + hipGetErrorString(e));
-    if (nominal->dloop_classes) (void)hipFree(nominal->dloop_classes);
-    nominal->dloop_classes = table;
-    nominal->dloop_cap = K;
-  }
+  if ((rc = mpcqp::grow_loop_classes(nominal, s)) != MPCQP_OK) return rc;
   mpcqp::LoopLaunch L{nullptr, f, steps};
   L.cls = cls;
-  L.K = K;
+  L.K = nominal->n_classes;
   return mpcqp::enqueue_fused_loop(nominal, relaxed, loop, "k_fleet_loop_mixed", MPCQP_LAUNCH_LOOP_MIXED, false, L, s);
 }
 

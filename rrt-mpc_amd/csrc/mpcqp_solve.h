@@ -2459,6 +2459,73 @@ __global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_swarm_loop_warm(
   fleet_loop_body<N, Pair, true, false, SwarmWarmWin>(P, f, steps, tr, b, lane, sm, ls, guess_passes);
 }
 
+// ------------------------------------------------------------------ fused swarm loop, a class per vehicle
+// mpcqp_swarm_loop_mixed: k_fleet_loop_mixed<N>'s dispatch (order, the range check of b, the class read)
+// around fleet_loop_body<N, false> on P + 2c, with the launch's LIVE replan trigger instead of `off`.  One
+// vehicle per wave.  Unlike k_fleet_loop_mixed, an ABORTED vehicle with replans left must reach the body's
+// to_replan, so the class is read for RUNNING vehicles and for ABORTED ones that can replan (the body's
+// own can_replan, from the same words); every other phase returns first with nothing read or written.  A
+// vehicle whose index lies outside [0, K) never indexes the table: RUNNING, it is ABORTED with status
+// MPCQP_BAD_CLASS and both masks 0; ABORTED, nothing of it is written; in both cases it does not reach
+// to_replan, so the replanning kernels between the launches skip it (they act on REPLAN_* phases only).
+// swarm_class: the vehicle's class, or -1 when the wave has nothing more to do.
+__device__ __forceinline__ int swarm_class(const int32_t* __restrict__ cls, int K, const mpcqp_fleet& f,
+                                           const mpcqp::LoopTrigger& tr, int b, int lane) {
+  const int V = f.vehicles;
+  const int ph = f.phase[b];
+  if (ph != MPCQP_FLEET_RUNNING) {
+    if (ph != MPCQP_FLEET_ABORTED) return -1;
+    if (!(tr.max_replans > 0 && tr.replans[b] >= 0 && tr.replans[b] < tr.max_replans)) return -1;
+  }
+  const int c = cls[b];
+  if ((unsigned)c >= (unsigned)K) {
+    if (ph == MPCQP_FLEET_RUNNING && lane == 0) {
+      f.phase[b] = MPCQP_FLEET_ABORTED;
+      f.status[b] = MPCQP_BAD_CLASS;
+      f.mask[b] = 0;
+      f.mask[(size_t)V + b] = 0;
+    }
+    return -1;
+  }
+  return c;
+}
+
+template <int N>
+__global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_swarm_loop_mixed(const mpcqp_params* __restrict__ P,
+                                                                               const int32_t* __restrict__ cls, int K,
+                                                                               mpcqp_fleet f, int steps,
+                                                                               mpcqp::LoopTrigger tr) {
+  __shared__ SolveLds<N> sm;
+  __shared__ double ls[6];  // loop state: x[4], u_prev[2]
+  const int b = tr.order ? tr.order[blockIdx.x] : (int)blockIdx.x;
+  const int lane = (int)threadIdx.x;
+  if (b < 0 || b >= f.vehicles) return;
+  const int c = swarm_class(cls, K, f, tr, b, lane);
+  if (c < 0) return;
+  fleet_loop_body<N, false>(P + 2 * (size_t)c, f, steps, tr, b, lane, sm, ls);
+}
+
+// SwarmMixedWarmWin: a vehicle of k_swarm_loop_mixed_warm: FleetWin exactly; a type of its own for
+// FleetCarryWin's reason.
+struct SwarmMixedWarmWin : FleetWin {};
+
+// mpcqp_swarm_loop_mixed_warm: the same dispatch around fleet_loop_body's Warm.  Ug starts as NaN in every
+// launch, as in k_swarm_loop_warm (a relaunched vehicle has a new reference).
+template <int N>
+__global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_swarm_loop_mixed_warm(
+    const mpcqp_params* __restrict__ P, const int32_t* __restrict__ cls, int K, mpcqp_fleet f, int steps,
+    mpcqp::LoopTrigger tr, int guess_passes) {
+  __shared__ SolveLds<N> sm;
+  __shared__ double ls[6];  // loop state: x[4], u_prev[2]
+  const int b = tr.order ? tr.order[blockIdx.x] : (int)blockIdx.x;
+  const int lane = (int)threadIdx.x;
+  if (b < 0 || b >= f.vehicles) return;
+  const int c = swarm_class(cls, K, f, tr, b, lane);
+  if (c < 0) return;
+  fleet_loop_body<N, false, true, false, SwarmMixedWarmWin>(P + 2 * (size_t)c, f, steps, tr, b, lane, sm, ls,
+                                                            guess_passes);
+}
+
 // ------------------------------------------------------------------ B = 1 server
 // One resident wave serving the sequential closed loop of TrajectoryTracker.track: it waits for the
 // host to raise box->req (system-scope loads of pinned host memory, s_sleep between polls), solves the
@@ -2628,6 +2695,17 @@ void launch_swarm_loop_warm(hipStream_t s, const LoopLaunch& L) {
   hipLaunchKernelGGL((k_swarm_loop_warm<N, false>), dim3(f.vehicles), dim3(kWave), 0, s, L.P, f, L.steps, L.tr,
                      L.guess_passes);
 }
+// the swarm's loops with a class per vehicle (L.cls, L.K) and the live trigger (L.tr); never paired
+template <int N>
+void launch_swarm_loop_mixed(hipStream_t s, const LoopLaunch& L) {
+  hipLaunchKernelGGL(k_swarm_loop_mixed<N>, dim3(L.f->vehicles), dim3(kWave), 0, s, L.P, L.cls, L.K, *L.f, L.steps,
+                     L.tr);
+}
+template <int N>
+void launch_swarm_loop_mixed_warm(hipStream_t s, const LoopLaunch& L) {
+  hipLaunchKernelGGL(k_swarm_loop_mixed_warm<N>, dim3(L.f->vehicles), dim3(kWave), 0, s, L.P, L.cls, L.K, *L.f,
+                     L.steps, L.tr, L.guess_passes);
+}
 // two QPs per wave from a caller's guess (N <= kPairMaxHorizon)
 template <int N>
 void launch_solve_pair_warm(hipStream_t s, const Launch& L) {
@@ -2648,7 +2726,7 @@ void launch_solve_pair(hipStream_t s, const Launch& L) {
 // instantiates the kernels).  A new per-horizon entry point: a member of HorizonKernels, and here.
 template <int LO, int HI>
 int register_horizons() {
-  HorizonKernels k{};  // by member name: five members share fleet_loop_t, and a swapped pair would compile
+  HorizonKernels k{};  // by member name: seven members share fleet_loop_t, and a swapped pair would compile
   k.solve = &launch_solve<LO>;
   k.mixed = &launch_solve_mixed<LO>;
   k.serve = &launch_serve<LO>;
@@ -2659,6 +2737,8 @@ int register_horizons() {
   k.serve_warm = &launch_serve_warm<LO>;
   k.loop_warm_carry = &launch_fleet_loop_warm_carry<LO>;
   k.swarm_warm = &launch_swarm_loop_warm<LO>;
+  k.swarm_mixed = &launch_swarm_loop_mixed<LO>;
+  k.swarm_mixed_warm = &launch_swarm_loop_mixed_warm<LO>;
   if constexpr (LO <= kPairMaxHorizon) {
     k.pair = &launch_solve_pair<LO>;
     k.pair_warm = &launch_solve_pair_warm<LO>;

@@ -22,6 +22,8 @@
 // (k_fleet_loop with the trigger: each vehicle steps until it triggers or ends) with the replanning
 // kernels in between -- no per-step launches.  mpcqp_swarm_loop_warm is the same rounds with
 // k_swarm_loop_warm: each vehicle's solves start from its step before, cold at the first step of a launch.
+// mpcqp_swarm_loop_mixed / _mixed_warm are the same rounds again with a parameter class per vehicle
+// (k_swarm_loop_mixed, k_swarm_loop_mixed_warm); the replanning kernels read no parameter block.
 #include "mpcqp_build.h"
 #include "mpcqp_plan.h"
 #include "mpcqp_refbuild.h"
@@ -270,30 +272,55 @@ int mpcqp_swarm_step(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f,
 // triggers or ends, the flagged ones are replanned; a vehicle's r-th trigger comes in round r - 1, so
 // the last round triggers none.  Cold, a parameter block without the fused loop runs the stepped swarm
 // to the end; warm, it is refused before anything is enqueued or invalidated.
+// mixed != nullptr (mpcqp_swarm_loop_mixed, mpcqp_swarm_loop_mixed_warm): the same rounds with a class per
+// vehicle (cls), k_swarm_loop_mixed / k_swarm_loop_mixed_warm under the two workspaces' class tables;
+// `mixed` names the caller in the refusals, and neither has a stepped fallback.
 static int swarm_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s, bool warm,
-                      int guess_passes, void* stream) {
+                      int guess_passes, void* stream, const char* mixed = nullptr, const int32_t* cls = nullptr) {
   int rc = check_swarm(f, s);
   if (rc) return rc;
   rc = mpcqp_fleet_loop(nominal, relaxed, f, 0, stream);  // the fleet's checks (no work at 0 steps)
   if (rc) return rc;
+  using HK = mpcqp::HorizonKernels;
   const mpcqp::fleet_loop_t loop = mpcqp::fused_loop(
-      nominal, relaxed, warm ? &mpcqp::HorizonKernels::swarm_warm : &mpcqp::HorizonKernels::loop);
+      nominal, relaxed, mixed ? (warm ? &HK::swarm_mixed_warm : &HK::swarm_mixed) : (warm ? &HK::swarm_warm : &HK::loop));
+  if (mixed && !loop)
+    return fail(MPCQP_E_HORIZON, std::string(mixed) + " runs the fused one-wave loop only (N <= 32, fast mode, no "
+                                                      "debug_state): the stepped swarm has no per-vehicle classes");
   if (warm && !loop)
     return fail(MPCQP_E_HORIZON, "mpcqp_swarm_loop_warm runs the fused one-wave loop only (N <= 32, fast mode, no "
                                  "debug_state): the stepped swarm takes no guess");
+  if (mixed) {
+    if ((rc = mpcqp::check_loop_classes(nominal, relaxed, mixed)) != MPCQP_OK) return rc;
+    // one dt: the replanning builds every vehicle's new reference with s->dt
+    for (const mpcqp_ws* ws : {nominal, relaxed})
+      for (size_t k = 0; k < ws->hclasses.size(); ++k)
+        if (ws->hclasses[k].dt != s->dt)
+          return fail(MPCQP_E_ARG, std::string(mixed) + ": class " + std::to_string(k) + " of the " +
+                                       (ws == nominal ? "nominal" : "relaxed") + " table has dt " +
+                                       std::to_string(ws->hclasses[k].dt) + ", the swarm " + std::to_string(s->dt) +
+                                       " (one dt: the replanning builds references with the swarm's)");
+  }
   if (f->vehicles == 0) return MPCQP_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (s->max_replans > 0 && (rc = set_replan_attrs(s)) != MPCQP_OK) return rc;
   if (!loop)  // mid / long horizons, reproducible or debug mode: the stepped swarm to the end
     return mpcqp_swarm_run(nominal, relaxed, f, s, f->max_steps, 1, stream);
+  if (mixed && (rc = mpcqp::grow_loop_classes(nominal, st)) != MPCQP_OK) return rc;
   mpcqp::LoopLaunch L{nullptr, f, f->max_steps, {s->replan_distance, s->max_replans, s->replans, s->start_goal}};
-  if (warm) {
-    L.guess_passes = guess_passes;
+  if (warm) L.guess_passes = guess_passes;
+  if (mixed) {
+    L.cls = cls;
+    L.K = nominal->n_classes;
+  } else if (warm) {
     L.tr.pair = mpcqp::use_pairs_warm(nominal);
   }
+  const char* name = mixed ? (warm ? "k_swarm_loop_mixed_warm" : "k_swarm_loop_mixed")
+                           : (warm ? "k_swarm_loop_warm" : "k_fleet_loop");
+  const int kind = mixed ? (warm ? MPCQP_LAUNCH_LOOP_MIXED_WARM : MPCQP_LAUNCH_LOOP_MIXED)
+                         : (warm ? MPCQP_LAUNCH_LOOP_WARM : MPCQP_LAUNCH_LOOP);
   for (int r = 0; r <= s->max_replans; ++r) {
-    rc = mpcqp::enqueue_fused_loop(nominal, relaxed, loop, warm ? "k_swarm_loop_warm" : "k_fleet_loop",
-                                   warm ? MPCQP_LAUNCH_LOOP_WARM : MPCQP_LAUNCH_LOOP, !warm, L, st);
+    rc = mpcqp::enqueue_fused_loop(nominal, relaxed, loop, name, kind, !warm && !mixed, L, st);
     if (rc) return rc;
     if (r < s->max_replans && (rc = enqueue_replan(f, s, st, false)) != MPCQP_OK) return rc;
   }
@@ -307,6 +334,18 @@ int mpcqp_swarm_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f,
 int mpcqp_swarm_loop_warm(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s,
                           int guess_passes, void* stream) {
   return swarm_loop(nominal, relaxed, f, s, true, guess_passes, stream);
+}
+
+int mpcqp_swarm_loop_mixed(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s,
+                           const int32_t* cls, void* stream) {
+  if (!cls) return fail(MPCQP_E_ARG, "null cls");
+  return swarm_loop(nominal, relaxed, f, s, false, 0, stream, "mpcqp_swarm_loop_mixed", cls);
+}
+
+int mpcqp_swarm_loop_mixed_warm(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s,
+                                const int32_t* cls, int guess_passes, void* stream) {
+  if (!cls) return fail(MPCQP_E_ARG, "null cls");
+  return swarm_loop(nominal, relaxed, f, s, true, guess_passes, stream, "mpcqp_swarm_loop_mixed_warm", cls);
 }
 
 int mpcqp_swarm_run(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s, int steps,

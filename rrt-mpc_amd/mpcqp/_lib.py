@@ -43,10 +43,11 @@ PAIRING_MODES = {"off": PAIR_OFF, "on": PAIR_ON, "auto": PAIR_AUTO}
 E_DEVICE = -6  # MPCQP_E_DEVICE: a fault surfaced at a stream synchronisation
 # mpcqp_launch_info: info[0], the kind of the last solver launch recorded on a workspace (MPCQP_LAUNCH_*)
 (LAUNCH_NONE, LAUNCH_SOLVE, LAUNCH_SOLVE_MIXED, LAUNCH_SOLVE_WARM, LAUNCH_LOOP, LAUNCH_LOOP_MIXED, LAUNCH_LOOP_WARM,
- LAUNCH_LOOP_WARM_CARRY) = range(8)
+ LAUNCH_LOOP_WARM_CARRY, LAUNCH_LOOP_MIXED_WARM) = range(9)
 LAUNCH_KINDS = {LAUNCH_NONE: "none", LAUNCH_SOLVE: "solve", LAUNCH_SOLVE_MIXED: "solve_mixed",
                 LAUNCH_SOLVE_WARM: "solve_warm", LAUNCH_LOOP: "loop", LAUNCH_LOOP_MIXED: "loop_mixed",
-                LAUNCH_LOOP_WARM: "loop_warm", LAUNCH_LOOP_WARM_CARRY: "loop_warm_carry"}
+                LAUNCH_LOOP_WARM: "loop_warm", LAUNCH_LOOP_WARM_CARRY: "loop_warm_carry",
+                LAUNCH_LOOP_MIXED_WARM: "loop_mixed_warm"}
 # warm start (mpcqp_solve_warm, mpcqp_fleet_loop_warm): polish passes the guess's attempt may take
 DEFAULT_GUESS_PASSES = 8  # the best of 1, 2, 3, 5, 8 at 4096 vehicles, N = 20 (profiles/warm_start/)
 
@@ -339,6 +340,11 @@ _SYMBOLS = {
     "mpcqp_solve_served_warm": ([ctypes.c_void_p, ctypes.c_int], ctypes.c_int),
     "mpcqp_swarm_loop_warm": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MpcqpFleet),
                                ctypes.POINTER(MpcqpSwarm), ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
+    "mpcqp_swarm_loop_mixed": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MpcqpFleet),
+                                ctypes.POINTER(MpcqpSwarm), ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+    "mpcqp_swarm_loop_mixed_warm": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MpcqpFleet),
+                                     ctypes.POINTER(MpcqpSwarm), ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p],
+                                    ctypes.c_int),
 }
 
 

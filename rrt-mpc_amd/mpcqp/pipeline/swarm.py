@@ -18,7 +18,10 @@ on the GPU with a per-step replan trigger.
                (max_replans + 1 launches, the replanning kernels between them).  With
                ``warm_start=True`` as well: ``mpcqp_swarm_loop_warm``, the same launches with each
                vehicle's solves started from its step before (cold at the first step of a launch, so
-               a replanned vehicle starts its new reference cold).
+               a replanned vehicle starts its new reference cold).  After
+               ``Swarm.set_classes`` (``fused=True``): ``mpcqp_swarm_loop_mixed`` /
+               ``mpcqp_swarm_loop_mixed_warm``, the same launches with a parameter class per vehicle
+               (``run(..., classes=)``).
 Every vehicle between replans follows the reference's single-vehicle loop exactly.
 """
 from __future__ import annotations
@@ -32,7 +35,7 @@ import numpy as np
 
 from .. import _lib
 from ..planning.rrt_star import BatchedRRTStarPlanner, PlannerParameters, pcg64_states
-from .fleet import FleetTracker
+from .fleet import FleetTracker, relaxed_parameters
 
 REPLAN_SEED_STRIDE = 7919  # replan r of vehicle v draws from default_rng(seed_v + 7919 (r + 1))
 
@@ -95,6 +98,39 @@ class Swarm:
         self.fused = bool(fused)
         self._L = _lib.lib()
 
+    def set_classes(self, params_list, settings=None, relaxed_settings=None) -> None:
+        """Per-vehicle parameter classes for the fused swarm (``mpcqp_swarm_loop_mixed``, with
+        ``warm_start=True`` ``mpcqp_swarm_loop_mixed_warm``): block k of the nominal controller is
+        ``params_list[k]``, block k of the retry ``relaxed_parameters(params_list[k])``; ``settings`` /
+        ``relaxed_settings`` as ``FleetTracker.set_classes`` takes them.  ``run(..., classes=cls)`` then
+        runs vehicle v under block ``cls[v]`` (class 0 without ``classes``).  ``None`` or ``[]`` drops the
+        tables: the swarm is homogeneous again.  Needs ``fused=True`` and a horizon of at most 32 (the
+        stepped swarm has no classes), and one dt: the replanning builds every vehicle's new reference
+        with the swarm's ``mpc.dt``, so every class must have it."""
+        fleet = self.fleet
+        if not params_list:
+            fleet._nominal.set_classes(None)
+            fleet._relaxed.set_classes(None)
+            fleet.num_classes = 0
+            fleet._class_params = None
+            return
+        if not self.fused:
+            raise ValueError("set_classes needs fused=True: only the fused swarm loop runs per-vehicle classes")
+        if fleet.horizon > 32:
+            raise ValueError(f"set_classes needs a horizon <= 32 (the fused loop), got {fleet.horizon}")
+        params_list = list(params_list)
+        for k, p in enumerate(params_list):
+            if float(p.dt) != float(self.mpc.dt):
+                raise ValueError(f"the swarm runs one dt: class {k} has dt {float(p.dt)}, the swarm's replanning "
+                                 f"builds references with mpc.dt = {float(self.mpc.dt)}")
+        # not through FleetTracker.set_classes: the swarm's tracker is built with fused=False (the swarm
+        # issues the fused calls itself) and would refuse
+        fleet._nominal.set_classes(params_list, settings)
+        fleet._relaxed.set_classes([relaxed_parameters(p) for p in params_list],
+                                   settings if relaxed_settings is None else relaxed_settings)
+        fleet.num_classes = len(params_list)
+        fleet._class_params = params_list
+
     def _plan(self, starts, goals, seeds):
         """Final paths of every problem (growth, extraction, pruning and smoothing on the device);
         returns (success mask, paths with the start alone where no plan was found)."""
@@ -155,7 +191,10 @@ class Swarm:
         return s, b
 
     def run(self, starts: np.ndarray, goals: np.ndarray, seeds=None, *, sim_steps: Optional[int] = None,
-            check_every: int = 10) -> SwarmResult:
+            check_every: int = 10, classes=None) -> SwarmResult:
+        """``classes`` (int array or int32 device tensor, shape ``(V,)``; after ``set_classes``): vehicle
+        v's block; an index outside the table aborts that vehicle with status ``BAD_CLASS`` and it never
+        replans.  Without ``classes`` a swarm with a table runs every vehicle under class 0."""
         torch = self.fleet._torch
         starts = np.asarray(starts, dtype=float).reshape(-1, 2)
         goals = np.asarray(goals, dtype=float).reshape(-1, 2)
@@ -167,7 +206,9 @@ class Swarm:
         planned, paths, found = self._plan(starts, goals, seeds)
         t["plan_s"] = time.perf_counter() - t0
         t0 = time.perf_counter()
-        self.fleet.reset_from_plans(paths, starts, goals, max_steps=total, device_reference=True)
+        mixed = classes is not None or bool(self.fleet.num_classes)  # classes without a table: refused below
+        ckw = dict(classes=self.fleet._class_indices(classes, V)) if mixed else {}
+        self.fleet.reset_from_plans(paths, starts, goals, max_steps=total, device_reference=True, **ckw)
         fb = self.fleet.buffers()
         if (~planned).any():  # no plan: the vehicle never starts (the reference raises, :69-72)
             fb["phase"][torch.from_numpy(np.flatnonzero(~planned)).to(self.device)] = _lib.FLEET_ABORTED
@@ -178,7 +219,12 @@ class Swarm:
         stream = torch.cuda.current_stream(self.device)
         done = 0
         if self.fused and V:
-            call, args = ("mpcqp_swarm_loop_warm", (self.guess_passes,)) if self.warm_start else ("mpcqp_swarm_loop", ())
+            if mixed:
+                call = "mpcqp_swarm_loop_mixed_warm" if self.warm_start else "mpcqp_swarm_loop_mixed"
+                args = (fb["cls"].data_ptr(),) + ((self.guess_passes,) if self.warm_start else ())
+            else:
+                call, args = (("mpcqp_swarm_loop_warm", (self.guess_passes,)) if self.warm_start
+                              else ("mpcqp_swarm_loop", ()))
             _lib.check(getattr(self._L, call)(self.fleet._nominal._ws, self.fleet._relaxed._ws,
                                               ctypes.byref(self.fleet._fleet), ctypes.byref(sw), *args,
                                               ctypes.c_void_p(stream.cuda_stream)), call)
@@ -253,14 +299,17 @@ def merge_swarm_results(parts: Sequence[SwarmResult]) -> SwarmResult:
 
 
 def run_swarm_sharded(run: Callable[..., SwarmResult], starts, goals, seeds, *, rank: int, world: int,
-                      all_gather_object: Callable[[list, object], None], **kwargs) -> SwarmResult:
+                      all_gather_object: Callable[[list, object], None], classes=None, **kwargs) -> SwarmResult:
     """Run rank's block of the swarm with ``run`` (``Swarm.run`` of this rank's device) and gather
-    every rank's result: each rank returns the whole swarm's result, in vehicle order."""
+    every rank's result: each rank returns the whole swarm's result, in vehicle order.  ``classes``
+    (``(V,)``, a mixed swarm) is cut like the seeds; None passes nothing to ``run``."""
     starts = np.asarray(starts, dtype=float).reshape(-1, 2)
     goals = np.asarray(goals, dtype=float).reshape(-1, 2)
     V = len(starts)
     seeds = np.arange(V) if seeds is None else np.asarray(seeds)
     lo, hi = shard_vehicles(V, world, rank)
+    if classes is not None:
+        kwargs["classes"] = classes[lo:hi]
     local = run(starts[lo:hi], goals[lo:hi], seeds=seeds[lo:hi], **kwargs) if hi > lo else None
     parts: list = [None] * world
     all_gather_object(parts, local)

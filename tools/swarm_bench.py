@@ -10,6 +10,11 @@ The warm start (Swarm(fused=True, warm_start=True)) against the cold fused swarm
 
     python tools/swarm_bench.py --warm [--guess-passes 8] [--reps 5] [--pairing auto|on|off]
 
+A mixed swarm (Swarm.set_classes, vehicle v under parameter block v mod K: mpcqp_swarm_loop_mixed, warm
+mpcqp_swarm_loop_mixed_warm) against its K homogeneous sub-swarms run back to back, cold and warm, interleaved:
+
+    python tools/swarm_bench.py --classes 4 [--reps 15] [--guess-passes 8]
+
 Multi-GPU (BASELINE config 5 on 8 GPUs): vehicles sharded over ranks (mpcqp.pipeline.swarm
 .run_swarm_sharded), one process per GPU, the per-vehicle results gathered at the end:
 
@@ -162,6 +167,81 @@ def warm_bench(a) -> None:
     print(json.dumps(out))
 
 
+def classes_bench(a) -> None:
+    """One mixed swarm (K classes, vehicle v in class v mod K, one launch per round) against the K homogeneous
+    sub-swarms of the same vehicles run back to back (K launches per round), cold and warm: whole Swarm.run
+    calls on the same starts, goals and seeds, the four legs alternating within every repeat in one process with
+    the order rotating from repeat to repeat; repeat 0 warms up.  Per leg: medians with min and max of
+    track_replan_s (summed over the sub-swarms on the split legs) and of the end-to-end time, vehicle-steps and
+    replans, and whether every vehicle's steps, phase and replan steps equal the mixed leg's."""
+    import torch
+    from fleet_bench import class_blocks
+
+    from mpcqp.config import MPCConfig
+    from mpcqp.pipeline.swarm import Swarm, merge_swarm_results
+    from mpcqp.planning.rrt_star import default_planner_parameters
+
+    occ = np.load(ROOT / "rrt-mpc_amd" / "mpcqp" / "data" / "default_plan.npz")["occupancy"]
+    prm = default_planner_parameters()
+    K = a.classes
+    gp = a.guess_passes[0]
+    out = {"metric": "Swarm.run seconds: one mixed swarm against its K homogeneous sub-swarms back to back, "
+                     "legs interleaved", "horizon": 15, "sim_steps": a.steps, "classes": K,
+           "replan_distance": a.replan_distance, "max_replans": a.max_replans, "guess_passes": gp, "reps": a.reps,
+           "runs": []}
+    mpc = MPCConfig(horizon=15, sim_steps=a.steps)
+    blocks = class_blocks(mpc.to_parameters(0.8), K)
+    for V in a.vehicles:
+        starts, goals = pairs(occ, V, 5)
+        cls = np.arange(V) % K
+        idx = [np.flatnonzero(cls == c) for c in range(K)]
+        order = np.concatenate(idx)
+        kw = dict(map_resolution=0.8, device="cuda:0", replan_distance=a.replan_distance, max_replans=a.max_replans,
+                  fused=True)
+        legs = {}
+        for temp, wkw in (("cold", {}), ("warm", dict(warm_start=True, guess_passes=gp))):
+            mixed = Swarm(occ, mpc, prm, max_vehicles=V, **kw, **wkw)
+            mixed.set_classes(blocks)
+            legs[f"mixed:{temp}"] = [(mixed, np.arange(V), dict(classes=cls))]
+            legs[f"split:{temp}"] = [(Swarm(occ, mpc, prm, max_vehicles=max(len(i), 1), params=blocks[c], **kw, **wkw),
+                                      i, {}) for c, i in enumerate(idx) if len(i)]
+        names = list(legs)
+        times = {k: {"track_replan_s": [], "end_to_end_s": []} for k in names}
+        res = {}
+        for r in range(a.reps + 1):  # repeat 0 warms up
+            for k in names[r % len(names):] + names[:r % len(names)]:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                parts = [sw.run(starts[i], goals[i], seeds=i, **more) for sw, i, more in legs[k]]
+                torch.cuda.synchronize()
+                if r:
+                    times[k]["end_to_end_s"].append(time.perf_counter() - t0)
+                    times[k]["track_replan_s"].append(sum(p.timings["track_replan_s"] for p in parts))
+                res[k] = parts
+        run = {"vehicles": V, "classes": K}
+        for k in names:
+            rk = merge_swarm_results(res[k])  # the split legs: class by class, i.e. in `order`
+            sel = np.arange(V) if k.startswith("mixed") else order
+            ref = merge_swarm_results(res["mixed:" + k.split(":")[1]])
+            info = legs[k][0][0].fleet._nominal.launch_info()
+            run[k] = {"launches_per_round": len(legs[k]), "vehicle_steps": int(rk.steps.sum()),
+                      "goal_reached": int((rk.phase == 1).sum()), "replans": int(rk.replans.sum()),
+                      "vehicles_replanned": int((rk.replans > 0).sum()), "launch": info["name"],
+                      "per_wave": info["per_wave"],
+                      "same_as_mixed": bool(np.array_equal(rk.steps, ref.steps[sel]) and np.array_equal(rk.phase, ref.phase[sel])
+                                            and np.array_equal(rk.replan_steps, ref.replan_steps[sel]))}
+            for what, ts in times[k].items():
+                med = float(np.median(ts))
+                run[k][what] = {"median": med, "min": min(ts), "max": max(ts), "all": ts,
+                                "over_mixed": med / float(np.median(times["mixed:" + k.split(":")[1]][what]))}
+        out["runs"].append(run)
+        for leg in legs.values():
+            for sw, _, _ in leg:
+                sw.fleet.close()
+        print(json.dumps(run), flush=True)
+    print(json.dumps(out))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--vehicles", type=int, nargs="+", default=[100, 1024])
@@ -180,7 +260,19 @@ def main() -> None:
     ap.add_argument("--reps", type=int, default=5, help="with --warm: timed repeats per leg, after a warm-up repeat")
     ap.add_argument("--pairing", default="auto", choices=["auto", "on", "off"],
                     help="with --warm: two vehicles per wave (mpcqp_set_pairing); a warm launch pairs under \"on\" only")
+    ap.add_argument("--classes", type=int, default=0,
+                    help="K > 0: one mixed swarm of K parameter classes (mpcqp_swarm_loop_mixed[_warm]) against its K "
+                         "homogeneous sub-swarms back to back, cold and warm, interleaved (--reps, --guess-passes)")
     a = ap.parse_args()
+    if a.classes:
+        if a.reps < 1:
+            ap.error("--reps must be >= 1")
+        if a.guess_passes is None:
+            from mpcqp import _lib
+
+            a.guess_passes = [_lib.DEFAULT_GUESS_PASSES]
+        classes_bench(a)
+        return
     if a.distributed:
         distributed(a)
         return
