@@ -298,13 +298,15 @@ int mpcqp_set_pairing(mpcqp_ws* ws, int mode);
  * side by side).  No counterpart in the reference (one MPCParameters per controller, one QP per call).
  * Additive to ABI 9: no existing struct or call changes.
  *
- * Limits: a mixed build never runs two QPs per wave (the halves of a wave would need two blocks):
- * mpcqp_set_pairing is ignored for it.  The B = 1 paths (mpcqp_solve_staged, mpcqp_solve_served), the
+ * Limits: under mpcqp_set_pairing a mixed build never runs two QPs per wave (the halves of a wave would
+ * need two blocks): that call is ignored for it, and it runs one QP per wave unless
+ * mpcqp_set_class_pairing (below) pairs QPs of one class, which share their block.  The B = 1 paths (mpcqp_solve_staged, mpcqp_solve_served), the
  * fleet (mpcqp_fleet_*) and the swarm (mpcqp_swarm_*) keep using the workspace's own block, whatever
  * table it holds.
  *
  * The one fleet call that reads the tables is mpcqp_fleet_loop_mixed (below, after mpcqp_fleet_loop): the
- * fused closed loop with a class per vehicle.  Fused loop only, never paired; the swarm is unchanged.
+ * fused closed loop with a class per vehicle.  Fused loop only, one vehicle per wave unless
+ * mpcqp_set_class_pairing; the swarm is unchanged.
  * The swarm calls that read the tables are calls of their own: mpcqp_swarm_loop_mixed and
  * mpcqp_swarm_loop_mixed_warm (below, after mpcqp_swarm_loop_warm).
  */
@@ -327,6 +329,44 @@ int mpcqp_set_classes(mpcqp_ws* ws, int K, const mpcqp_params* blocks);
  * of the launch are solved as usual.  A later plain mpcqp_build returns the workspace to its own block. */
 int mpcqp_build_mixed(mpcqp_ws* ws, int B, const double* x0, const double* ref, const double* u_prev,
                       const int32_t* cls, void* stream);
+
+/*
+ * Mixed launches at two per wave (additive to ABI 9): QPs or vehicles of the SAME class share a wave, so
+ * the wave's parameter block stays one block and the results stay those of the one-per-wave mixed launch
+ * bit for bit.  No counterpart in the reference.
+ *
+ * mpcqp_class_slots: the pairing itself, standalone (no workspace, no allocation; safe inside a stream
+ * capture).  One small kernel writes slots[2w], slots[2w + 1], the two members of wave w, for the
+ * mpcqp_class_slot_waves(V, K) = (V + min(K + 1, V)) / 2 waves of the grid; -1 marks an empty half.
+ *   - every index of [0, V) -- every entry of seq (V int32, device), if seq is given -- appears exactly
+ *     once; every other entry is -1 (the whole table is written by every call);
+ *   - the two members of a wave have the same class cls[v] (V int32, device); indices whose class lies
+ *     outside [0, K) (and entries of seq outside [0, V), whose class is not read) form one further bucket
+ *     and are paired with each other;
+ *   - at most one wave per bucket has an empty half: (V + number of odd buckets) / 2 waves are used, the
+ *     rest of the grid holds -1 / -1;
+ *   - waves are laid out class by class; within a class they follow seq in chunks of 1024 entries (the
+ *     order inside a chunk is not defined), so a longest-first seq stays longest-first across chunks.
+ * K must lie in [1, MPCQP_CLASS_SLOT_MAX_CLASSES] (the pass is one workgroup with a counter per class in
+ * LDS), V >= 0, cls and slots non-null: MPCQP_E_ARG otherwise.  mpcqp_class_slot_waves is host arithmetic
+ * (0 for V <= 0 or K < 0) and knows no cap.
+ */
+#define MPCQP_CLASS_SLOT_MAX_CLASSES 4095
+int mpcqp_class_slots(int V, int K, const int32_t* cls, const int32_t* seq, int32_t* slots, void* stream);
+int mpcqp_class_slot_waves(int V, int K);
+
+/* on = 1: the mixed launches of this workspace -- mpcqp_solve after mpcqp_build_mixed, and
+ * mpcqp_fleet_loop_mixed with this workspace as `nominal` -- run two QPs (vehicles) of one class per
+ * wave: the slot kernel on the launch's stream (over the identity, or over the longest-first dispatch
+ * order where mpcqp_fleet_loop_mixed applies it), then the paired mixed kernel on
+ * mpcqp_class_slot_waves(B, K) workgroups, recorded with 2 per wave and that many workgroups
+ * (mpcqp_launch_info).  Only where the paired one-wave kernels exist (N <= 15, fast mode, no debug_state)
+ * and K <= MPCQP_CLASS_SLOT_MAX_CLASSES; every other mixed launch runs one per wave exactly as with
+ * on = 0, the default.  Independent of mpcqp_set_pairing, which mixed launches keep ignoring.  The
+ * swarm's mixed calls and every warm call stay at one per wave (class) whatever this switch says.
+ * The first on = 1 allocates the workspace's slot table (2 x max_batch int32), so it cannot run inside
+ * a stream capture (MPCQP_E_STATE); mpcqp_destroy frees it.  NULL ws, or on not 0 or 1: MPCQP_E_ARG. */
+int mpcqp_set_class_pairing(mpcqp_ws* ws, int on);
 
 /*
  * Closed-loop fleet: V vehicles tracking their own references, one MPC step each per call
@@ -403,9 +443,10 @@ int mpcqp_fleet_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f,
  * written; the other vehicles run as usual.  A vehicle that is not RUNNING is skipped before its class
  * is read.
  * Limits: the fused loop only -- N <= 32 in fast mode without debug_state; other parameter blocks
- * return MPCQP_E_HORIZON, and then nothing is enqueued and nothing invalidated.  Never paired: a mixed
- * loop runs one vehicle per wave whatever mpcqp_set_pairing says (two vehicles of different classes per
- * wave would need two blocks).  The replan trigger is off and the swarm is unchanged (its replanning
+ * return MPCQP_E_HORIZON, and then nothing is enqueued and nothing invalidated.  Never paired by
+ * mpcqp_set_pairing, whatever its mode (two vehicles of different classes per wave would need two blocks):
+ * a mixed loop runs one vehicle per wave unless mpcqp_set_class_pairing on `nominal` pairs vehicles of one
+ * class, which need one.  The replan trigger is off and the swarm is unchanged (its replanning
  * builds references with one dt).  Out of scope: mixed mpcqp_fleet_step / mpcqp_fleet_run (and with
  * them horizons above 32, reproducible mode and debug_state: the stepped path would need a mask and a
  * model input in the three mixed solve kernels), the swarm, and the B = 1 paths.  (A mixed fleet that

@@ -196,9 +196,15 @@ int ensure_buffers(mpcqp_ws* ws, bool model, bool state, hipStream_t s) {
   if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("hipMalloc (workspace buffers): ") + hipGetErrorString(e));
   return MPCQP_OK;
 }
+bool use_class_pairs(const mpcqp_ws* ws) {
+  const HorizonKernels* k = one_wave(ws->p);
+  return ws->class_pairing && ws->dslots && k && k->pair_mixed && ws->n_classes >= 1 &&
+         ws->n_classes <= MPCQP_CLASS_SLOT_MAX_CLASSES;
+}
 bool use_pairs(const mpcqp_ws* ws, int count) {
-  // a mixed build (mpcqp_build_mixed) never pairs: the two halves of a wave would need two parameter
-  // blocks, which turns every parameter into a per-lane value
+  // a mixed build (mpcqp_build_mixed) never pairs under these modes: the two halves of a wave would need
+  // two parameter blocks, which turns every parameter into a per-lane value (pairs of one class:
+  // use_class_pairs)
   if (ws->build.cls) return false;
   const HorizonKernels* k = one_wave(ws->p);
   if (!k || !k->pair) return false;
@@ -329,6 +335,7 @@ void mpcqp_destroy(mpcqp_ws* ws) {
   (void)hipFree(ws->dorder);
   (void)hipFree(ws->dclasses);
   (void)hipFree(ws->dloop_classes);
+  (void)hipFree(ws->dslots);
   ws->serve_box.release();
   ws->stage_in.release();
   ws->stage_out.release();
@@ -342,6 +349,27 @@ int mpcqp_set_pairing(mpcqp_ws* ws, int mode) {
   if (mode != MPCQP_PAIR_OFF && mode != MPCQP_PAIR_ON && mode != MPCQP_PAIR_AUTO)
     return fail(MPCQP_E_ARG, "pairing mode must be MPCQP_PAIR_OFF, _ON or _AUTO");
   ws->pairing = mode;
+  return MPCQP_OK;
+}
+
+int mpcqp_set_class_pairing(mpcqp_ws* ws, int on) {
+  if (!ws) return fail(MPCQP_E_ARG, "null ws");
+  if (on != 0 && on != 1) return fail(MPCQP_E_ARG, "class pairing must be 0 or 1");
+  if (on && !ws->dslots) {
+    // the slot table is allocated here, which a stream capture cannot record (mpcqp_set_classes' check)
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(nullptr, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
+      (void)hipGetLastError();
+      return fail(MPCQP_E_STATE, "mpcqp_set_class_pairing inside a stream capture");
+    }
+    const mpcqp::DeviceGuard dev(ws->device);
+    hipError_t e = dev.err;
+    if (e == hipSuccess) e = hipMalloc(&ws->dslots, 2 * sizeof(int32_t) * (size_t)ws->max_batch);
+    if (e == hipErrorStreamCaptureUnsupported || e == hipErrorStreamCaptureImplicit)
+      return fail(MPCQP_E_STATE, "mpcqp_set_class_pairing inside a stream capture");
+    if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("hipMalloc (class slots): ") + hipGetErrorString(e));
+  }
+  ws->class_pairing = on != 0;
   return MPCQP_OK;
 }
 
@@ -386,8 +414,8 @@ int mpcqp_build_mixed(mpcqp_ws* ws, int B, const double* x0, const double* ref, 
 }
 
 // a solve launch's return code, recorded for mpcqp_launch_info where the launch went out
-static int recorded(mpcqp_ws* ws, int rc, int kind, int per_wave, int B) {
-  if (rc == MPCQP_OK) ws->launched_as(kind, per_wave, B);
+static int recorded(mpcqp_ws* ws, int rc, int kind, int per_wave, int B, int workgroups = -1) {
+  if (rc == MPCQP_OK) ws->launched_as(kind, per_wave, B, workgroups);
   return rc;
 }
 
@@ -404,10 +432,17 @@ int mpcqp_solve(mpcqp_ws* ws, int B, double* u0, double* X, double* U, int32_t* 
   L.x0 = built.x0;
   L.ref = built.ref;
   L.u_prev = built.u_prev;
-  if (built.cls) {  // the last build was mpcqp_build_mixed: a parameter block per QP, never paired
+  if (built.cls) {  // the last build was mpcqp_build_mixed: a parameter block per QP
     L.table = ws->dclasses;
     L.cls = built.cls;
     L.K = ws->n_classes;
+    if (L.ref && mpcqp::use_class_pairs(ws)) {  // mpcqp_set_class_pairing: two QPs of one class per wave
+      L.slots = ws->dslots;
+      mpcqp::enqueue_class_slots(B, L.K, L.cls, nullptr, ws->dslots, s);
+      mpcqp::one_wave(ws->p)->pair_mixed(s, L);
+      return recorded(ws, mpcqp::launched("k_solve_pair_mixed"), MPCQP_LAUNCH_SOLVE_MIXED, 2, B,
+                      mpcqp::class_slot_waves(B, L.K));
+    }
     // the workgroup-per-QP launchers read L.cls themselves; the one-wave kernel has an entry of its own
     (k ? k->mixed : mpcqp::launcher(ws->p))(s, L);
     return recorded(ws, mpcqp::launched("k_solve_mixed"), MPCQP_LAUNCH_SOLVE_MIXED, 1, B);

@@ -527,6 +527,9 @@ struct Launch {
   const mpcqp_params* table = nullptr;
   const int32_t* cls = nullptr;
   int K = 0;
+  // mpcqp_set_class_pairing: the slot table of k_class_slots over this batch (2 x mpcqp_class_slot_waves(B, K)
+  // entries), two QPs of one class per wave (k_solve_pair_mixed)
+  const int32_t* slots = nullptr;
   // a caller's guess (mpcqp_solve_warm): B x 2 x N in the layout of U, and the attempt's pass limit
   const double* guess = nullptr;
   int guess_passes = 0;
@@ -534,6 +537,13 @@ struct Launch {
 
 typedef void (*launcher_t)(hipStream_t, const Launch&);
 constexpr int kPairMaxHorizon = 15;  // n = 2N <= 30: two QPs per wave
+// mpcqp_class_slot_waves: the grid of a class-paired mixed launch, (V + min(K + 1, V)) / 2 -- at least
+// the used waves (V + odd buckets) / 2 of the K + 1 buckets, at most V
+inline int class_slot_waves(int V, int K) {
+  if (V <= 0 || K < 0) return 0;
+  const long long buckets = (long long)K + 1;
+  return (int)(((long long)V + (buckets < V ? buckets : (long long)V)) / 2);
+}
 // The config-5 replan trigger inside the fused loop (mpcqp_swarm_loop): after each step a RUNNING
 // vehicle farther than replan_distance from ref[path_idx], or an ABORTED one, with replans left leaves
 // the loop as MPCQP_FLEET_REPLAN_* with its replanning problem in start_goal.  max_replans = 0: off.
@@ -587,6 +597,9 @@ struct LoopLaunch {
   LoopTrigger tr;
   const int32_t* cls = nullptr;  // a class per vehicle (V indices) into the K classes
   int K = 0;
+  // mpcqp_set_class_pairing (with cls): the workspace's slot table, set by the caller and filled on the
+  // stream by enqueue_fused_loop; two vehicles of one class per wave (k_fleet_loop_pair_mixed)
+  int32_t* slots = nullptr;
   int guess_passes = 0;  // the warm loop's pass limit per attempt
   double* carry = nullptr;  // k_fleet_loop_warm_carry: the carried guess, V x 2 x N (nullable)
 };
@@ -600,7 +613,9 @@ typedef void (*fleet_loop_t)(hipStream_t, const LoopLaunch&);
 // nullptr above kPairMaxHorizon) and k_fleet_loop_warm_carry (the warm loop with the guess carried across
 // launches; its launcher runs two vehicles per wave where tr.pair) and k_swarm_loop_warm (the warm loop
 // with the swarm's live replan trigger; two per wave where tr.pair), k_swarm_loop_mixed and
-// k_swarm_loop_mixed_warm (the swarm's cold and warm loops with a class per vehicle; never paired).  The object that instantiates a
+// k_swarm_loop_mixed_warm (the swarm's cold and warm loops with a class per vehicle; never paired), and
+// k_solve_pair_mixed (a parameter block per QP, two QPs of one class per wave; nullptr above kPairMaxHorizon --
+// its loop counterpart k_fleet_loop_pair_mixed is launched by loop_mixed where L.slots is set).  The object that instantiates a
 // horizon registers it from a namespace-scope initialiser (register_horizons, mpcqp_solve.h: member by
 // member, since seven of them share one type); an all-null entry is a horizon not compiled in.
 struct HorizonKernels {
@@ -614,6 +629,7 @@ struct HorizonKernels {
   fleet_loop_t loop_warm_carry;
   fleet_loop_t swarm_warm;
   fleet_loop_t swarm_mixed, swarm_mixed_warm;
+  launcher_t pair_mixed;
 };
 // fills entry N of the table in mpcqp.hip (constant-initialised, so the order of the objects'
 // initialisers does not matter)
@@ -625,6 +641,12 @@ void register_horizon(int N, const HorizonKernels& k);
 const HorizonKernels* one_wave(const mpcqp_params& p, bool debug_ok = false);
 // k_solve_pair / k_fleet_loop<N, true> for `count` QPs or vehicles of this workspace's launch?
 bool use_pairs(const mpcqp_ws* ws, int count);
+// k_solve_pair_mixed / k_fleet_loop_pair_mixed for a mixed launch of this workspace (its class table)?
+// Under mpcqp_set_class_pairing, where the paired kernels exist (N <= 15, fast mode, no debug_state) and
+// the table has at most MPCQP_CLASS_SLOT_MAX_CLASSES classes.  Defined in mpcqp.hip.
+bool use_class_pairs(const mpcqp_ws* ws);
+// mpcqp_class_slots after its argument checks (mpcqp_fleet.hip): the slot kernel on the stream
+void enqueue_class_slots(int V, int K, const int32_t* cls, const int32_t* seq, int32_t* slots, hipStream_t s);
 // the long-horizon solve (N >= MPCQP_WIDE_MIN_HORIZON; mpcqp_wide.hip): one 256-thread workgroup
 // per QP, L.state = its workspace (wide_stride(N) doubles per QP)
 void launch_solve_wide(hipStream_t s, const Launch& L);
@@ -757,13 +779,18 @@ struct mpcqp_ws {
   // dloop_cap classes, filled from the two class tables by a kernel on the launch stream at every call
   mpcqp_params* dloop_classes = nullptr;
   int dloop_cap = 0;
+  // mpcqp_set_class_pairing: mixed launches pair within classes; the slot table (2 x max_batch entries),
+  // allocated there and written by k_class_slots on the launch stream
+  bool class_pairing = false;
+  int32_t* dslots = nullptr;
   // mpcqp_launch_info: the last solver launch recorded here {MPCQP_LAUNCH_*, QPs (vehicles) per wave,
   // workgroups, B or V}; host bookkeeping, written by launched_as() and cleared by mpcqp_set_params
   int32_t last_launch[4] = {MPCQP_LAUNCH_NONE, 0, 0, 0};
-  void launched_as(int kind, int per_wave, int count) {
+  // workgroups < 0: count / per_wave rounded up (a class-paired launch runs the slot table's grid instead)
+  void launched_as(int kind, int per_wave, int count, int workgroups = -1) {
     last_launch[0] = kind;
     last_launch[1] = per_wave;
-    last_launch[2] = (count + per_wave - 1) / per_wave;
+    last_launch[2] = workgroups >= 0 ? workgroups : (count + per_wave - 1) / per_wave;
     last_launch[3] = count;
   }
   void no_launch() { last_launch[0] = last_launch[1] = last_launch[2] = last_launch[3] = 0; }

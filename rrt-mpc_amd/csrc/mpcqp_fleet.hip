@@ -167,6 +167,67 @@ __global__ __launch_bounds__(kOrderBuckets) void k_fleet_order(mpcqp_fleet f, in
   for (int v = t; v < V; v += kOrderBuckets) order[atomicAdd(&cnt[bucket(v)], 1)] = v;
 }
 
+// mpcqp_class_slots: the two members of each wave of a class-paired mixed launch (k_solve_pair_mixed,
+// k_fleet_loop_pair_mixed).  Bucket k < K holds the entries of class k, bucket K those whose class lies
+// outside [0, K) (and entries outside [0, V), whose class is not read); bucket k owns the waves
+// [base_k, base_k + (cnt_k + 1) / 2), base the running sum over the buckets before it, and its members
+// fill those waves' slots in the order of the sequence, chunk by chunk (within a chunk of 1024 entries
+// the cursor's atomics decide; the members are independent, k_fleet_order's argument).  The odd slot of a
+// bucket and the waves past the used ones are written -1 by the threads that know them, so every entry of
+// the table is written exactly once.  One 1024-thread workgroup: a counter per bucket in LDS (kSlotBuckets
+// = MPCQP_CLASS_SLOT_MAX_CLASSES + 1, kSlotRun consecutive ones per thread) and a scan over the threads'
+// sums.
+constexpr int kSlotThreads = 1024;
+constexpr int kSlotBuckets = MPCQP_CLASS_SLOT_MAX_CLASSES + 1;
+constexpr int kSlotRun = kSlotBuckets / kSlotThreads;
+static_assert(kSlotRun * kSlotThreads == kSlotBuckets, "a whole number of buckets per thread");
+__global__ __launch_bounds__(kSlotThreads) void k_class_slots(int V, int K, int W, const int32_t* __restrict__ cls,
+                                                              const int32_t* __restrict__ seq,
+                                                              int32_t* __restrict__ slots) {
+  __shared__ int cnt[kSlotBuckets];  // members per bucket, then the bucket's slot cursor
+  __shared__ int part[kSlotThreads];
+  const int t = threadIdx.x;
+  auto member = [&](int i) { return seq ? seq[i] : i; };
+  auto bucket = [&](int v) {
+    if (v < 0 || v >= V) return K;
+    const int c = cls[v];
+    return (unsigned)c < (unsigned)K ? c : K;
+  };
+  for (int k = t; k < kSlotBuckets; k += kSlotThreads) cnt[k] = 0;
+  __syncthreads();
+  for (int i = t; i < V; i += kSlotThreads) atomicAdd(&cnt[bucket(member(i))], 1);
+  __syncthreads();
+  // waves per bucket, summed over this thread's run (buckets past K are empty), scanned over the threads
+  int own = 0;
+  for (int j = 0; j < kSlotRun; ++j) own += (cnt[t * kSlotRun + j] + 1) >> 1;
+  part[t] = own;
+  __syncthreads();
+  for (int d = 1; d < kSlotThreads; d <<= 1) {  // inclusive scan (Hillis-Steele)
+    const int add = t >= d ? part[t - d] : 0;
+    __syncthreads();
+    part[t] += add;
+    __syncthreads();
+  }
+  int base = part[t] - own;  // the first wave of this thread's run
+  const int used = part[kSlotThreads - 1];
+  for (int j = 0; j < kSlotRun; ++j) {
+    const int k = t * kSlotRun + j, n = cnt[k];
+    if (n & 1) slots[2 * base + n] = -1;  // the bucket's empty half
+    cnt[k] = 2 * base;
+    base += (n + 1) >> 1;
+  }
+  for (int i = 2 * used + t; i < 2 * W; i += kSlotThreads) slots[i] = -1;  // the grid past the used waves
+  __syncthreads();
+  for (int i0 = 0; i0 < V; i0 += kSlotThreads) {  // a chunk at a time: its members stay ahead of the next chunk's
+    const int i = i0 + t;
+    if (i < V) {
+      const int v = member(i);
+      slots[atomicAdd(&cnt[bucket(v)], 1)] = v;
+    }
+    __syncthreads();
+  }
+}
+
 int check_fleet(const mpcqp_ws* nom, const mpcqp_ws* rel, const mpcqp_fleet* f) {
   if (!nom || !rel || !f) return fail(MPCQP_E_ARG, "null argument");
   if (nom == rel) return fail(MPCQP_E_ARG, "nominal and relaxed workspaces must differ");
@@ -212,6 +273,17 @@ int run_graph(mpcqp_ws* nom, mpcqp_ws* rel, const mpcqp_fleet* f, int steps, hip
 
 extern "C" {
 
+int mpcqp_class_slot_waves(int V, int K) { return mpcqp::class_slot_waves(V, K); }
+
+int mpcqp_class_slots(int V, int K, const int32_t* cls, const int32_t* seq, int32_t* slots, void* stream) {
+  if (V < 0 || !cls || !slots) return fail(MPCQP_E_ARG, "mpcqp_class_slots needs V >= 0, cls and slots");
+  if (K < 1 || K > MPCQP_CLASS_SLOT_MAX_CLASSES)
+    return fail(MPCQP_E_ARG, "mpcqp_class_slots: K outside [1, " + std::to_string(MPCQP_CLASS_SLOT_MAX_CLASSES) + "]");
+  if (V == 0) return MPCQP_OK;
+  mpcqp::enqueue_class_slots(V, K, cls, seq, slots, static_cast<hipStream_t>(stream));
+  return mpcqp::launched("k_class_slots");
+}
+
 int mpcqp_fleet_step(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, void* stream) {
   int rc = check_fleet(nominal, relaxed, f);
   if (rc) return rc;
@@ -222,6 +294,11 @@ int mpcqp_fleet_step(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f,
 }  // extern "C"
 
 namespace mpcqp {
+void enqueue_class_slots(int V, int K, const int32_t* cls, const int32_t* seq, int32_t* slots, hipStream_t s) {
+  hipLaunchKernelGGL(k_class_slots, dim3(1), dim3(kSlotThreads), 0, s, V, K, class_slot_waves(V, K), cls, seq,
+                     slots);
+}
+
 int fleet_buffers(mpcqp_ws* nominal, mpcqp_ws* relaxed, hipStream_t s) {
   int rc = ensure_buffers(nominal, true, needs_state(nominal->p), s);
   if (rc == MPCQP_OK) rc = ensure_buffers(relaxed, true, needs_state(relaxed->p), s);
@@ -326,9 +403,15 @@ int enqueue_fused_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, fleet_loop_t loop, 
     L.tr.order = nominal->dorder;
   }
   if (may_pair) L.tr.pair = use_pairs(nominal, L.f->vehicles);
+  if (L.cls && L.slots) {  // mpcqp_set_class_pairing: pairs within classes, over the dispatch order where there is one
+    enqueue_class_slots(L.f->vehicles, L.K, L.cls, L.tr.order, L.slots, s);
+    L.tr.pair = true;
+  }
   loop(s, L);
   const int rc = launched(name);
-  if (rc == MPCQP_OK) nominal->launched_as(kind, L.tr.pair ? 2 : 1, L.f->vehicles);
+  if (rc == MPCQP_OK)
+    nominal->launched_as(kind, L.tr.pair ? 2 : 1, L.f->vehicles,
+                         L.cls && L.slots ? class_slot_waves(L.f->vehicles, L.K) : -1);
   return rc;
 }
 }  // namespace mpcqp
@@ -365,6 +448,7 @@ int mpcqp_fleet_loop_mixed(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fle
   mpcqp::LoopLaunch L{nullptr, f, steps};
   L.cls = cls;
   L.K = nominal->n_classes;
+  if (mpcqp::use_class_pairs(nominal)) L.slots = nominal->dslots;  // two vehicles of one class per wave
   return mpcqp::enqueue_fused_loop(nominal, relaxed, loop, "k_fleet_loop_mixed", MPCQP_LAUNCH_LOOP_MIXED, false, L, s);
 }
 

@@ -2079,6 +2079,54 @@ __global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_solve_mixed(cons
                          U);
 }
 
+// PairClassWin: a QP of k_solve_pair_mixed: ServeWin exactly (the lane within the half, opaque); a type of
+// its own for ClassWin's reason.
+struct PairClassWin {
+  static constexpr bool kFleet = false;
+  int ln;
+  __device__ __forceinline__ int lane() const { return ln; }
+};
+
+// ------------------------------------------------------------------ K2, a parameter block per QP, two QPs per wave
+// A mixed batch under mpcqp_set_class_pairing (N <= 15): k_solve_pair's layout with the two QPs of a wave
+// taken from the slot table of k_class_slots (mpcqp_fleet.hip) instead of 2w and 2w + 1: half h of
+// workgroup w solves QP slots[2w + h], and the table pairs QPs of one class only.  The block therefore
+// stays what it is in k_solve_mixed, wave-uniform scalar data, copied once per wave; each half runs
+// solve_one's driver on its own LDS block: k_solve_mixed's results bit for bit.  A half whose slot is -1
+// (the odd QP of a class, a wave past the used ones) returns alone; so does one whose class lies
+// outside [0, K), after its first lane -- thread 32 in half 1 -- has written MPCQP_BAD_CLASS and zero
+// iters (class_ok's report; such QPs are paired with each other, so either half, both or neither
+// may be one).  The wave's class is read from the first lane that is left.
+template <int N>
+__global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_solve_pair_mixed(
+    const mpcqp_params* __restrict__ P, const int32_t* __restrict__ cls, const int32_t* __restrict__ slots, int K,
+    int B, const double* __restrict__ in_x0, const double* __restrict__ in_ref, const double* __restrict__ in_up,
+    double* __restrict__ u0o, double* __restrict__ Xo, double* __restrict__ Uo, int32_t* __restrict__ statuso,
+    int32_t* __restrict__ iterso, uint8_t* __restrict__ activeo) {
+  static_assert(2 * N <= 30, "two QPs per wave need n = 2N <= 30 (a padding lane or two per half)");
+  __shared__ SolveLds<N, true> sm[2];
+  const int h = threadIdx.x >> 5;
+  const int b = slots[2 * blockIdx.x + h];
+  if (b < 0 || b >= B) return;  // that half only: the other QP runs on
+  int ln = threadIdx.x & 31;
+  asm volatile("" : "+v"(ln));
+  const int c = cls[b];
+  if ((unsigned)c >= (unsigned)K) {
+    if ((threadIdx.x & 31) == 0) {
+      statuso[b] = MPCQP_BAD_CLASS;
+      if (iterso)
+        for (int i = 0; i < 4; ++i) iterso[(size_t)b * 4 + i] = 0;
+    }
+    return;
+  }
+  // one class per wave (the slot table's contract): uniform, so the copy below is scalar loads
+  const int cw = __builtin_amdgcn_readfirstlane(c);
+  const mpcqp_params p = P[cw];  // a copy, not a reference into the table: k_solve_mixed's reason
+  double U;
+  solve_one<N, PairClassWin, true>(p, b, nullptr, in_x0, in_ref, in_up, PairClassWin{ln}, sm[h], u0o, Xo, Uo,
+                                   statuso, iterso, activeo, U);
+}
+
 // ------------------------------------------------------------------ K2 from a caller's guess
 // mpcqp_solve_warm: QP b starts from row b of U_guess (B x 2 x N, the layout of the U output) through
 // solve_one's warm driver: one polish attempt from the guess, and the cold solve of k_solve where it
@@ -2187,8 +2235,10 @@ struct CarryRow<false> {};
 // with it; paired, the other half of its wave goes on alone, as after a goal.
 // WarmWin: the window type of the warm solves (a type per kernel family, FleetCarryWin's reason); the
 // cold loops never name it.
+// ColdWin: the window type of the cold solves, FleetWin for every loop but k_fleet_loop_pair_mixed (a type
+// per kernel family again).
 template <int N, bool Pair, bool Warm = false, bool Carry = false,
-          class WarmWin = std::conditional_t<Carry, FleetCarryWin, FleetWin>>
+          class WarmWin = std::conditional_t<Carry, FleetCarryWin, FleetWin>, class ColdWin = FleetWin>
 __device__ __forceinline__ void fleet_loop_body(const mpcqp_params* __restrict__ P, const mpcqp_fleet& f, int steps,
                                                 const mpcqp::LoopTrigger& tr, int b, int lane,
                                                 SolveLds<N, Pair>& sm, double* const ls, int guess_passes = 0,
@@ -2267,6 +2317,10 @@ __device__ __forceinline__ void fleet_loop_body(const mpcqp_params* __restrict__
                                                   f.status + (size_t)relax * V, nullptr, nullptr, Ul,
                                                   Guess<true>{g, guess_passes});
         }
+      } else if constexpr (!std::is_same_v<ColdWin, FleetWin>) {
+        st = solve_one<N, ColdWin, Pair>(p, b, nullptr, nullptr, nullptr, nullptr, ColdWin{win}, sm,
+                                         f.u0 + (size_t)relax * V * 2, f.X, nullptr,
+                                         f.status + (size_t)relax * V, nullptr, nullptr, Ul);
       } else {
         st = solve_one<N, FleetWin, Pair>(p, b, nullptr, nullptr, nullptr, nullptr, win, sm,
                                           f.u0 + (size_t)relax * V * 2, f.X, nullptr,
@@ -2388,6 +2442,51 @@ __global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_fleet_loop_mixed
   }
   const mpcqp::LoopTrigger off{0.0, 0, nullptr, nullptr};
   fleet_loop_body<N, false>(P + 2 * (size_t)c, f, steps, off, b, lane, sm, ls);
+}
+
+// FleetClassPairWin: a vehicle of k_fleet_loop_pair_mixed: FleetWin exactly; a type of its own for
+// FleetCarryWin's reason.
+struct FleetClassPairWin : FleetWin {};
+
+// ------------------------------------------------------------------ fused closed loop, a class per vehicle, two per wave
+// mpcqp_fleet_loop_mixed under mpcqp_set_class_pairing (N <= 15): k_fleet_loop_mixed's dispatch per half
+// around fleet_loop_body<N, true> on P + 2c, with the dead trigger.  Half h of workgroup w runs vehicle
+// slots[2w + h] of k_class_slots' table (built over the dispatch order, so longest first holds within
+// a class), which pairs vehicles of one class only: c is uniform over the wave and the offset stays one
+// scalar add.  Per half, in k_fleet_loop_mixed's order: the slot (-1: an empty half), the range check,
+// RUNNING before the class is read, then the MPCQP_BAD_CLASS abort from the half's first lane.  A half
+// that leaves here, or leaves the step loop first, lets the other run on alone, as in k_fleet_loop<N, true>
+// (one wave per workgroup: the body's barriers hold nobody).  The vehicle's buffers are
+// k_fleet_loop_mixed's bit for bit.
+template <int N>
+__global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_fleet_loop_pair_mixed(
+    const mpcqp_params* __restrict__ P, const int32_t* __restrict__ cls, int K, mpcqp_fleet f, int steps,
+    const int32_t* __restrict__ slots) {
+  static_assert(2 * N <= 30, "two vehicles per wave need n = 2N <= 30");
+  __shared__ SolveLds<N, true> smv[2];
+  __shared__ double lsv[12];  // loop state: x[4], u_prev[2] per half
+  const int h = (int)(threadIdx.x >> 5);
+  SolveLds<N, true>& sm = smv[h];
+  double* const ls = lsv + 6 * h;
+  const int b = slots[2 * (int)blockIdx.x + h];
+  const int lane = (int)(threadIdx.x & 31);
+  const int V = f.vehicles;
+  if (b < 0 || b >= V) return;
+  if (f.phase[b] != MPCQP_FLEET_RUNNING) return;
+  const int c = cls[b];
+  if ((unsigned)c >= (unsigned)K) {
+    if (lane == 0) {
+      f.phase[b] = MPCQP_FLEET_ABORTED;
+      f.status[b] = MPCQP_BAD_CLASS;
+      f.mask[b] = 0;
+      f.mask[(size_t)V + b] = 0;
+    }
+    return;
+  }
+  const int cw = __builtin_amdgcn_readfirstlane(c);  // one class per wave (the slot table's contract)
+  const mpcqp::LoopTrigger off{0.0, 0, nullptr, nullptr};
+  fleet_loop_body<N, true, false, false, FleetWin, FleetClassPairWin>(P + 2 * (size_t)cw, f, steps, off, b, lane, sm,
+                                                                      ls);
 }
 
 // ------------------------------------------------------------------ fused closed loop, warm started
@@ -2653,6 +2752,13 @@ void launch_fleet_loop(hipStream_t s, const LoopLaunch& L) {
 }
 template <int N>
 void launch_fleet_loop_mixed(hipStream_t s, const LoopLaunch& L) {
+  if constexpr (N <= kPairMaxHorizon) {
+    if (L.slots) {  // mpcqp_set_class_pairing: two vehicles of one class per wave, the slot table's grid
+      hipLaunchKernelGGL(k_fleet_loop_pair_mixed<N>, dim3(class_slot_waves(L.f->vehicles, L.K)), dim3(kWave), 0,
+                         s, L.P, L.cls, L.K, *L.f, L.steps, L.slots);
+      return;
+    }
+  }
   hipLaunchKernelGGL(k_fleet_loop_mixed<N>, dim3(L.f->vehicles), dim3(kWave), 0, s, L.P, L.cls, L.K, *L.f, L.steps,
                      L.tr.order);
 }
@@ -2721,6 +2827,14 @@ void launch_solve_pair(hipStream_t s, const Launch& L) {
                      L.u_prev, L.u0, L.X, L.U, L.st, L.it, L.ac);
 }
 
+// two QPs of one class per wave (L.slots; N <= kPairMaxHorizon, fused K1)
+template <int N>
+void launch_solve_pair_mixed(hipStream_t s, const Launch& L) {
+  static_assert(N <= kPairMaxHorizon, "a half-wave holds n = 2N <= 30 variables");
+  hipLaunchKernelGGL(k_solve_pair_mixed<N>, dim3(class_slot_waves(L.B, L.K)), dim3(kWave), 0, s, L.table, L.cls,
+                     L.slots, L.K, L.B, L.x0, L.ref, L.u_prev, L.u0, L.X, L.U, L.st, L.it, L.ac);
+}
+
 // Registers the kernels of horizons LO..HI with the table in mpcqp.hip; called from a namespace-scope
 // initialiser of the object that is to hold them (taking the launchers' addresses there is what
 // instantiates the kernels).  A new per-horizon entry point: a member of HorizonKernels, and here.
@@ -2742,6 +2856,7 @@ int register_horizons() {
   if constexpr (LO <= kPairMaxHorizon) {
     k.pair = &launch_solve_pair<LO>;
     k.pair_warm = &launch_solve_pair_warm<LO>;
+    k.pair_mixed = &launch_solve_pair_mixed<LO>;
   }
   register_horizon(LO, k);
   if constexpr (LO < HI) return register_horizons<LO + 1, HI>();

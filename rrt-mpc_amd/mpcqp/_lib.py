@@ -174,6 +174,8 @@ def class_table(params_list, method="admm", settings=None):
     return table
 
 
+CLASS_SLOT_MAX_CLASSES = 4095  # MPCQP_CLASS_SLOT_MAX_CLASSES: the most classes mpcqp_class_slots pairs within
+CLASS_PAIRING_MODES = {"off": 0, "on": 1}  # mpcqp_set_class_pairing
 REF_BAD_PATH = -2147483648
 REF_MAX_POINTS = 6144
 FLEET_RUNNING = 0
@@ -335,6 +337,10 @@ _SYMBOLS = {
     "mpcqp_fleet_loop_warm_carry": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MpcqpFleet), ctypes.c_int,
                                      ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "mpcqp_launch_info": ([ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
+    "mpcqp_class_slots": ([ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                           ctypes.c_void_p], ctypes.c_int),
+    "mpcqp_class_slot_waves": ([ctypes.c_int, ctypes.c_int], ctypes.c_int),
+    "mpcqp_set_class_pairing": ([ctypes.c_void_p, ctypes.c_int], ctypes.c_int),
     "mpcqp_stage_guess": ([ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)], ctypes.c_int),
     "mpcqp_solve_staged_warm": ([ctypes.c_void_p, ctypes.c_int], ctypes.c_int),
     "mpcqp_solve_served_warm": ([ctypes.c_void_p, ctypes.c_int], ctypes.c_int),
@@ -418,6 +424,8 @@ __all__ = [
     "to_c_params",
     "class_table",
     "BAD_CLASS",
+    "CLASS_SLOT_MAX_CLASSES",
+    "CLASS_PAIRING_MODES",
     "REF_BAD_PATH",
     "REF_MAX_POINTS",
     "FLEET_RUNNING",

@@ -135,12 +135,14 @@ class BatchedMPCController:
 
     Mixed batches: ``set_classes([params_0, ..., params_{K-1}])`` gives the workspace a table of K
     parameter blocks of this horizon, and ``solve_batch(..., classes=cls)`` solves QP b under block
-    ``cls[b]`` in the same single launch (``mpcqp_build_mixed``; never paired).  ``solve_one``, the
-    fleet and the swarm keep using the controller's own block.
+    ``cls[b]`` in the same single launch (``mpcqp_build_mixed``).  A mixed launch ignores ``pairing`` and
+    runs one QP per wave unless ``class_pairing="on"`` (``mpcqp_set_class_pairing``): then two QPs of the
+    same class share a wave for N <= 15, the same results bit for bit, and ``launch_info()`` reports
+    ``per_wave == 2``.  ``solve_one``, the fleet and the swarm keep using the controller's own block.
     """
 
     def __init__(self, params, max_batch: int, *, device=None, method: str = "admm", pairing: str = "auto",
-                 **settings) -> None:
+                 class_pairing: str = "off", **settings) -> None:
         import torch
 
         if method not in ("admm", "newton"):
@@ -166,6 +168,9 @@ class BatchedMPCController:
         self._ws = ws
         self.num_classes = 0
         self.set_pairing(pairing)
+        self.class_pairing = "off"
+        if class_pairing != "off":
+            self.set_class_pairing(class_pairing)
         N, B = self.horizon, self.max_batch
         kw = dict(device=self.device)
         self._u0 = torch.empty((B, 2), dtype=torch.float64, **kw)
@@ -188,6 +193,17 @@ class BatchedMPCController:
             raise ValueError(f"pairing must be one of {sorted(_lib.PAIRING_MODES)}")
         _lib.check(self._L.mpcqp_set_pairing(self._ws, _lib.PAIRING_MODES[mode]), "mpcqp_set_pairing")
         self.pairing = mode
+
+    def set_class_pairing(self, mode: str) -> None:
+        """Mixed launches at two per wave: "on" pairs QPs (in ``FleetTracker``'s nominal controller: vehicles)
+        of the same class for N <= 15, "off" (default) keeps a mixed launch at one per wave
+        (``mpcqp_set_class_pairing``; synchronous the first time it is "on": it allocates the slot table)."""
+        if mode not in _lib.CLASS_PAIRING_MODES:
+            raise ValueError(f"class_pairing must be one of {sorted(_lib.CLASS_PAIRING_MODES)}")
+        with self._torch.cuda.device(self.device):
+            _lib.check(self._L.mpcqp_set_class_pairing(self._ws, _lib.CLASS_PAIRING_MODES[mode]),
+                       "mpcqp_set_class_pairing")
+        self.class_pairing = mode
 
     def launch_info(self) -> dict:
         """What the last solver launch recorded on this controller's workspace did (``mpcqp_launch_info``;

@@ -124,7 +124,9 @@ class FleetTracker:
 
     ``pairing`` ("auto", "on", "off"; passed on to both controllers): two vehicles per wave for N <= 15 in
     the fused loops, the same buffers bit for bit.  The warm loops pair under "on" only; "auto" leaves
-    them at one vehicle per wave.
+    them at one vehicle per wave.  A fleet with classes (``set_classes``) ignores it and runs one vehicle
+    per wave unless ``class_pairing="on"`` (handed to the nominal controller, ``mpcqp_set_class_pairing``):
+    then two vehicles of the same class share a wave for N <= 15, the same buffers bit for bit.
     """
 
     warm_start = False
@@ -135,7 +137,8 @@ class FleetTracker:
     def __init__(self, mpc, *, map_resolution: float, max_vehicles: int, max_ref_len: int,
                  device=None, use_graph: bool = True, fused: bool = False,
                  relaxed_settings: Optional[dict] = None, params=None, warm_start: bool = False,
-                 guess_passes: Optional[int] = None, carry_guess: bool = False, **settings) -> None:
+                 guess_passes: Optional[int] = None, carry_guess: bool = False, class_pairing: str = "off",
+                 **settings) -> None:
         import torch
 
         from ..control.mpc_controller import BatchedMPCController
@@ -163,7 +166,8 @@ class FleetTracker:
         # defaults to closed_loop_settings (the caller's settings win)
         loop = closed_loop_settings(self.horizon)
         settings = {**loop, **settings}
-        self._nominal = BatchedMPCController(self.params, self.max_vehicles, device=device, **settings)
+        self._nominal = BatchedMPCController(self.params, self.max_vehicles, device=device,
+                                             class_pairing=class_pairing, **settings)
         # the retry's solver settings default to the nominal ones (control_stage.py:50-56 changes
         # only du_bounds and the reference speed)
         rs = settings if relaxed_settings is None else {**loop, **relaxed_settings}

@@ -11,8 +11,10 @@ reference-style host loop (TrajectoryTracker.track, one B=1 solve per step) on o
 --classes K: a heterogeneous fleet (vehicle v runs under parameter block v mod K) in ONE launch
 (mpcqp_fleet_loop_mixed) against the same vehicles as K homogeneous fused sub-fleets launched back to
 back (mpcqp_fleet_loop each, --pairing applies to them); K = 1 measures the mixed kernel against the plain
-fused loop.  The two sides alternate within every repeat, first in one order, then in the other; the
-references are loaded before the timed window, which holds the loop launches up to a synchronise.
+fused loop.  --class-pairing on off: the mixed launch also with two vehicles of one class per wave
+(mpcqp_set_class_pairing, N <= 15; side "mixed_paired").  The sides alternate within every repeat, the order
+rotating from repeat to repeat; the references are loaded before the timed window, which holds the loop
+launches up to a synchronise.
 
 --warm: the cold fused loop against the warm-started one, interleaved in one process (warm_bench).  With
 several --pairing modes every mode gets a cold and a warm side (--pairing on off: cold paired, warm paired,
@@ -64,7 +66,8 @@ def mixed_bench(a) -> None:
     dev = torch.device("cuda:0")
     K = a.classes
     out = {"metric": "closed-loop vehicle-steps/s, loop launches only", "horizon": a.horizon, "sim_steps": a.steps,
-           "classes": K, "pairing_of_sub_fleets": a.pairing, "reps_per_order": a.reps, "runs": []}
+           "classes": K, "pairing_of_sub_fleets": a.pairing, "class_pairing": a.class_pairing,
+           "reps_per_order": a.reps, "runs": []}
     mpc = MPCConfig(horizon=a.horizon, sim_steps=a.steps)
     blocks = class_blocks(mpc.to_parameters(0.8), K)
     for V in a.vehicles:
@@ -72,13 +75,17 @@ def mixed_bench(a) -> None:
         cls = np.arange(V) % K
         groups = [np.flatnonzero(cls == c) for c in range(K)]
         kw = dict(map_resolution=0.8, max_ref_len=160, device=dev, fused=True)
-        mixed = FleetTracker(mpc, max_vehicles=V, **kw)
-        mixed.set_classes(blocks)
+        mixes = {("mixed_paired" if mode == "on" else "mixed"): FleetTracker(mpc, max_vehicles=V, class_pairing=mode, **kw)
+                 for mode in a.class_pairing}
+        for ft in mixes.values():
+            ft.set_classes(blocks)
+        mixed = next(iter(mixes.values()))
         subs = [FleetTracker(mpc, max_vehicles=len(g), params=blocks[c], pairing=a.pairing, **kw)
                 for c, g in enumerate(groups)]
 
         def load():
-            mixed.reset_from_plans(paths, starts, goals, device_reference=True, classes=cls)
+            for ft in mixes.values():
+                ft.reset_from_plans(paths, starts, goals, device_reference=True, classes=cls)
             for ft, g in zip(subs, groups):
                 ft.reset_from_plans([paths[i] for i in g], starts[g], goals[g], device_reference=True)
 
@@ -90,12 +97,12 @@ def mixed_bench(a) -> None:
             torch.cuda.synchronize()
             return time.perf_counter() - t0
 
-        times = {"mixed": [], "split": []}
-        for r in range(2 * a.reps + 1):  # repeat 0 warms up; then the order alternates
+        names = ["split", *mixes]
+        times = {k: [] for k in [*mixes, "split"]}
+        for r in range(2 * a.reps + 1):  # repeat 0 warms up; then the order rotates
             load()
-            order = ("mixed", "split") if r % 2 else ("split", "mixed")
-            for side in order:
-                dt = timed([mixed] if side == "mixed" else subs)
+            for side in names[r % len(names):] + names[:r % len(names)]:
+                dt = timed([mixes[side]] if side in mixes else subs)
                 if r:
                     times[side].append(dt)
         rm = mixed.result()
@@ -109,13 +116,18 @@ def mixed_bench(a) -> None:
         for side, ts in times.items():
             run[side] = {"seconds_median": float(np.median(ts)), "seconds_min": min(ts), "seconds_max": max(ts),
                          "seconds": ts, "value": vsteps / float(np.median(ts))}
-        run["mixed_over_split_time"] = run["mixed"]["seconds_median"] / run["split"]["seconds_median"]
+        for side, ft in mixes.items():
+            info, rs = ft._nominal.launch_info(), ft.result()
+            run[side].update(per_wave=info["per_wave"], workgroups=info["workgroups"],
+                             same_steps_and_phases=bool((rs.steps == rm.steps).all() and (rs.phase == rm.phase).all()))
+            run[f"{side}_over_split_time"] = run[side]["seconds_median"] / run["split"]["seconds_median"]
+        if len(mixes) == 2:
+            run["mixed_paired_over_mixed_time"] = run["mixed_paired"]["seconds_median"] / run["mixed"]["seconds_median"]
         # per class: vehicle-steps and the longest vehicle (what sets a sub-launch's tail)
         run["per_class"] = [{"vehicles": len(g), "vehicle_steps": int(rm.steps[g].sum()),
                              "max_steps": int(rm.steps[g].max())} for g in groups]
         out["runs"].append(run)
-        mixed.close()
-        for ft in subs:
+        for ft in [*mixes.values(), *subs]:
             ft.close()
         print(json.dumps(run), flush=True)
     print(json.dumps(out))
@@ -219,6 +231,9 @@ def main() -> None:
                          "guess (mpcqp_fleet_loop_warm_carry)")
     ap.add_argument("--classes", type=int, default=0,
                     help="K > 0: one mixed fused launch (mpcqp_fleet_loop_mixed) against K homogeneous fused launches")
+    ap.add_argument("--class-pairing", nargs="+", default=["off"], choices=["on", "off"],
+                    help="with --classes: the mixed launch at one vehicle per wave (off), at two of one class per wave "
+                         "(on, mpcqp_set_class_pairing), or both as sides of their own")
     ap.add_argument("--warm", action="store_true",
                     help="the cold fused loop against the warm-started one (mpcqp_fleet_loop_warm), interleaved")
     ap.add_argument("--guess-passes", type=int, nargs="+", default=None,

@@ -13,7 +13,14 @@ handle), so two libraries can be timed in one process with the same host code:
   nine_plain     what a user did before: nine plain workspaces, one per block, solved one after another
                  on the same stream, each with the QPs of its class (the same QPs as mixed_k9)
 
+With --class-pairing (N <= 15: mpcqp_set_class_pairing; --classes K takes the first K blocks) three more legs
+join the rotation, and the slot kernel is timed on its own (mpcqp_class_slots over this batch, device events):
+
+  mixed_kK_paired   the mixed launch with two QPs of one class per wave (the same bits as mixed_kK)
+  K_plain_paired    the K plain workspaces under MPCQP_PAIR_ON: the paired launches a mixed one replaces
+
     python tools/mixed_bench.py [--parent-lib PATH] [--out profiles/mixed_classes/bench.json]
+    python tools/mixed_bench.py --horizon 15 --batch 16384 --classes 4 --class-pairing --out FILE
 
 One JSON document: every repeat of every leg (ms per step), the leg order, both build ids.
 """
@@ -46,7 +53,7 @@ def _bind(path, names):
 class Workspace:
     """One mpcqp workspace with its device inputs and outputs, driven through the C-ABI."""
 
-    def __init__(self, handle, cparams, x0, ref, up, stream, table=None, cls=None):
+    def __init__(self, handle, cparams, x0, ref, up, stream, table=None, cls=None, pairing=None, class_pairing=False):
         import torch
 
         self.h, self.B, self.s = handle, int(x0.shape[0]), ctypes.c_void_p(stream.cuda_stream)
@@ -64,6 +71,10 @@ class Workspace:
         self.active = torch.empty((self.B, 5 * N + 1), dtype=torch.uint8, device=dev)
         if table is not None:
             self._check(handle.mpcqp_set_classes(self.ws, len(table), table), "mpcqp_set_classes")
+        if pairing is not None:  # MPCQP_PAIR_*
+            self._check(handle.mpcqp_set_pairing(self.ws, pairing), "mpcqp_set_pairing")
+        if class_pairing:
+            self._check(handle.mpcqp_set_class_pairing(self.ws, 1), "mpcqp_set_class_pairing")
 
     def _check(self, rc, what):
         if rc != 0:
@@ -110,6 +121,9 @@ def main() -> None:
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--parent-lib", type=Path, default=None,
                     help="libmpcqp.so built from the parent commit (leg plain_parent; skipped when absent)")
+    ap.add_argument("--classes", type=int, default=9, help="the first K blocks of tests/param_variants.py VARIANTS")
+    ap.add_argument("--class-pairing", action="store_true",
+                    help="add the class-paired mixed leg and the K plain launches under MPCQP_PAIR_ON (N <= 15)")
     ap.add_argument("--out", type=Path, default=ROOT / "profiles" / "mixed_classes" / "bench.json")
     a = ap.parse_args()
     import torch
@@ -122,12 +136,17 @@ def main() -> None:
         raise SystemExit("mixed_bench needs a GPU (no CPU fallback, no CPU timing)")
     B, N = a.batch, a.horizon
     base_names = ["mpcqp_create", "mpcqp_destroy", "mpcqp_build", "mpcqp_solve", "mpcqp_last_error", "mpcqp_build_id"]
-    new = _bind(_lib.LIB_PATH, base_names + ["mpcqp_set_classes", "mpcqp_build_mixed"])
+    new = _bind(_lib.LIB_PATH, base_names + ["mpcqp_set_classes", "mpcqp_build_mixed", "mpcqp_set_pairing",
+                                             "mpcqp_set_class_pairing", "mpcqp_class_slots", "mpcqp_class_slot_waves",
+                                             "mpcqp_launch_info"])
     parent = _bind(a.parent_lib, base_names) if a.parent_lib else None
     batch = scenarios.config3(B, horizon=N)
     base = MPCConfig(horizon=N).to_parameters(0.8)
-    blocks = [variant(MPCConfig(horizon=N).to_parameters(resolution(v)), v) for v in VARIANTS]
+    if not 2 <= a.classes <= len(VARIANTS):
+        raise SystemExit(f"--classes must lie in [2, {len(VARIANTS)}]")
+    blocks = [variant(MPCConfig(horizon=N).to_parameters(resolution(v)), v) for v in VARIANTS[:a.classes]]
     K = len(blocks)
+    mixed_k, k_plain = f"mixed_k{K}", "nine_plain" if K == 9 else f"{K}_plain"
     cls9 = (np.arange(B) % K).astype(np.int32)
     stream = torch.cuda.current_stream(torch.device("cuda:0"))
     inputs = (batch.x0, batch.ref, batch.u_prev)
@@ -135,13 +154,19 @@ def main() -> None:
     legs = {
         "plain": [Workspace(new, cbase, *inputs, stream)],
         "mixed_k1": [Workspace(new, cbase, *inputs, stream, _lib.class_table([base]), np.zeros(B, np.int32))],
-        "mixed_k9": [Workspace(new, cbase, *inputs, stream, _lib.class_table(blocks), cls9)],
-        "nine_plain": [Workspace(new, _lib.to_c_params(p), *(x[cls9 == c] for x in inputs), stream)
+        mixed_k: [Workspace(new, cbase, *inputs, stream, _lib.class_table(blocks), cls9)],
+        k_plain: [Workspace(new, _lib.to_c_params(p), *(x[cls9 == c] for x in inputs), stream)
                        for c, p in enumerate(blocks)],
     }
     if parent is not None:
         legs["plain_parent"] = [Workspace(parent, cbase, *inputs, stream)]
-    order = [k for k in ("plain", "plain_parent", "mixed_k1", "mixed_k9", "nine_plain") if k in legs]
+    if a.class_pairing:
+        legs[mixed_k + "_paired"] = [Workspace(new, cbase, *inputs, stream, _lib.class_table(blocks), cls9,
+                                               class_pairing=True)]
+        legs[k_plain + "_paired"] = [Workspace(new, _lib.to_c_params(p), *(x[cls9 == c] for x in inputs), stream,
+                                               pairing=_lib.PAIRING_MODES["on"]) for c, p in enumerate(blocks)]
+    order = [k for k in ("plain", "plain_parent", "mixed_k1", mixed_k, mixed_k + "_paired", k_plain,
+                         k_plain + "_paired") if k in legs]
     ms = {k: [] for k in order}
     for _ in range(a.repeats):  # the legs alternate: every repeat visits each once, in this order
         for k in order:
@@ -151,17 +176,39 @@ def main() -> None:
     solved = {k: int(sum(int((w.status == 1).sum()) for w in legs[k])) for k in order}
     same = {"mixed_k1_equals_plain_bitwise": all(torch.equal(getattr(legs["mixed_k1"][0], f), getattr(legs["plain"][0], f))
                                                  for f in ("u0", "X", "U", "status", "iters", "active"))}
-    m9 = legs["mixed_k9"][0]
-    same["mixed_k9_equals_nine_plain_bitwise"] = all(
+    m9 = legs[mixed_k][0]
+    same[f"{mixed_k}_equals_{k_plain}_bitwise"] = all(
         torch.equal(getattr(m9, f)[torch.from_numpy(cls9 == c).to(m9.status.device)], getattr(w, f))
-        for c, w in enumerate(legs["nine_plain"]) for f in ("u0", "X", "U", "status", "iters", "active"))
+        for c, w in enumerate(legs[k_plain]) for f in ("u0", "X", "U", "status", "iters", "active"))
+    launches, slot_us = {}, None
+    if a.class_pairing:
+        mp = legs[mixed_k + "_paired"][0]
+        same[f"{mixed_k}_paired_equals_{mixed_k}_bitwise"] = all(
+            torch.equal(getattr(mp, f), getattr(m9, f)) for f in ("u0", "X", "U", "status", "iters", "active"))
+        for k in (mixed_k, mixed_k + "_paired", k_plain + "_paired"):  # what ran: QPs per wave, workgroups
+            info = (ctypes.c_int32 * 4)()
+            new.mpcqp_launch_info(legs[k][0].ws, info)
+            launches[k] = {"per_wave": int(info[1]), "workgroups": int(info[2]), "count": int(info[3])}
+        # the slot kernel alone, over this batch's classes: device events around `steps` calls, `repeats` times
+        slots = torch.empty(2 * new.mpcqp_class_slot_waves(B, K), dtype=torch.int32, device="cuda:0")
+        s = ctypes.c_void_p(stream.cuda_stream)
+        slot_us = []
+        for _ in range(a.repeats):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(a.steps):
+                new.mpcqp_class_slots(B, K, mp.cls.data_ptr(), None, slots.data_ptr(), s)
+            e1.record(stream)
+            e1.synchronize()
+            slot_us.append(1e3 * e0.elapsed_time(e1) / a.steps)
     if parent is not None:
         same["plain_equals_parent_bitwise"] = all(
             torch.equal(getattr(legs["plain_parent"][0], f), getattr(legs["plain"][0], f))
             for f in ("u0", "X", "U", "status", "iters", "active"))
     med = {k: float(np.median(v)) for k, v in ms.items()}
     out = {
-        "workload": f"config3, B = {B}, N = {N}; nine classes = tests/param_variants.py VARIANTS, cls[b] = b % 9",
+        "workload": f"config3, B = {B}, N = {N}; {K} classes = the first {K} of tests/param_variants.py VARIANTS, "
+                    f"cls[b] = b % {K}",
         "device": torch.cuda.get_device_name(0),
         "timing": f"device events around {a.steps} timed steps after {a.warmup} warm steps; {a.repeats} repeats per "
                   "leg, legs alternating within one process",
@@ -175,9 +222,15 @@ def main() -> None:
         "solved_qps": solved,
         "results": same,
         "ratio_mixed_k1_to_plain": med["mixed_k1"] / med["plain"],
-        "ratio_mixed_k9_to_nine_plain": med["mixed_k9"] / med["nine_plain"],
+        f"ratio_{mixed_k}_to_{k_plain}": med[mixed_k] / med[k_plain],
         "ratio_plain_to_parent": med["plain"] / med["plain_parent"] if parent is not None else None,
     }
+    if a.class_pairing:
+        out["launches"] = launches
+        out["slot_kernel_us"] = slot_us
+        out["slot_kernel_us_median"] = float(np.median(slot_us))
+        out[f"ratio_{mixed_k}_paired_to_{mixed_k}"] = med[mixed_k + "_paired"] / med[mixed_k]
+        out[f"ratio_{mixed_k}_paired_to_{k_plain}_paired"] = med[mixed_k + "_paired"] / med[k_plain + "_paired"]
     for ws in legs.values():
         for w in ws:
             w.close()
