@@ -510,6 +510,8 @@ int mpcqp_fleet_loop_warm_carry(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcq
 #define MPCQP_LAUNCH_LOOP_WARM 6
 #define MPCQP_LAUNCH_LOOP_WARM_CARRY 7
 #define MPCQP_LAUNCH_LOOP_MIXED_WARM 8 /* mpcqp_swarm_loop_mixed_warm (the cold call records LOOP_MIXED) */
+/* 9: the fused launches of mpcqp_swarm_loop_map (the swarm on a changing map, below) */
+#define MPCQP_LAUNCH_LOOP_MAP (MPCQP_LAUNCH_LOOP_MIXED_WARM + 1)
 int mpcqp_launch_info(const mpcqp_ws* ws, int32_t info[4]);
 
 /*
@@ -724,6 +726,64 @@ int mpcqp_swarm_loop_mixed(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fle
  * a guess kept across a replan or between calls, two vehicles of different classes per wave. */
 int mpcqp_swarm_loop_mixed_warm(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s,
                                 const int32_t* cls, int guess_passes, void* stream);
+
+/*
+ * The swarm on a changing map (additive to ABI 9): grids by epoch, and a replan trigger that looks ahead
+ * along the reference for newly occupied cells.  No existing struct or call changes; mpcqp_swarm_step,
+ * _run and every mpcqp_swarm_loop* above keep planning on s->occupancy alone.
+ *
+ * Time.  A vehicle's time is its own step count k = steps[v] (every vehicle starts at 0, one step is dt,
+ * replanning takes no time), and a vehicle that has taken k steps lives on
+ * grid min(k / epoch_steps, T - 1) (integer division, T = num_grids): the last grid holds for ever.
+ *
+ * Blocked test.  Evaluated exactly where the off-track test is: after a step, for a RUNNING vehicle with
+ * replans left and a valid ref_len / path_idx, on the state, path_idx and k after the step.  The
+ * off-track test comes first; where it fires the cause is MPCQP_REPLAN_OFF_TRACK.  Otherwise, for
+ * j = 0 .. lookahead - 1: row r = min(path_idx + j, ref_len - 1) of the vehicle's reference, cell
+ * xi = clamp(rint(ref[r].x), 0, W - 1), yi = clamp(rint(ref[r].y), 0, H - 1) -- the planner's own lookup,
+ * round half to even, clipped -- and the vehicle is blocked (MPCQP_REPLAN_BLOCKED) if any such cell of
+ * grid(k) is 0.  lookahead 0: no blocked test.  replan_distance <= 0 switches off only the off-track test.
+ *
+ * Replan.  A triggered vehicle, whatever the cause -- an ABORTED one picked up at the start of a launch
+ * included (MPCQP_REPLAN_ABORTED) -- writes grid_of[v] = grid(k) and, where replan_cause is given, its cause
+ * into replan_cause[v * max_replans + replans[v]].  The tree growth and the path extraction / shortcut
+ * pruning of that replan read grids + grid_of[v] * H * W; smoothing, build_reference and the commit are
+ * the swarm's own.  s->occupancy is not read by these two calls and may be NULL.
+ *
+ * mpcqp_swarm_run_map is mpcqp_swarm_run with this trigger and these grids (stepped; use_graph as there);
+ * mpcqp_swarm_loop_map is mpcqp_swarm_loop with them: max_replans + 1 launches of the fused loop with
+ * both tests inside (the lookahead rows tested by one lane each, one whole-wave vote), the replanning
+ * kernels between them.  The same operations per vehicle in both, so every fleet and swarm output buffer,
+ * replan_cause and grid_of of the fused call equal the stepped call's to the end bit for bit; with one
+ * grid and lookahead 0 they equal mpcqp_swarm_loop's / mpcqp_swarm_run's bit for bit; and a vehicle that
+ * never triggers equals the same vehicle of mpcqp_swarm_loop (vehicles are independent).
+ * The fused call runs one vehicle per wave whatever mpcqp_set_pairing says, cold only, no classes; each
+ * launch records as MPCQP_LAUNCH_LOOP_MAP on `nominal` (mpcqp_launch_info), the stepped call records
+ * nothing.  Parameter blocks without the fused one-wave loop (N > 32, reproducible, debug_state) make
+ * mpcqp_swarm_loop_map run mpcqp_swarm_run_map(max_steps, graph), as mpcqp_swarm_loop runs mpcqp_swarm_run.
+ * Errors, each before anything is enqueued, written or invalidated: NULL m, num_grids < 1,
+ * epoch_steps < 1, lookahead outside [0, 64], NULL grids, NULL grid_of with max_replans > 0: MPCQP_E_ARG.
+ * All other checks are mpcqp_swarm_loop's / mpcqp_swarm_run's (but for s->occupancy).  Out of scope: warm
+ * start, parameter classes and two vehicles per wave on a changing map, segment tests between rows.
+ */
+#define MPCQP_REPLAN_ABORTED 1
+#define MPCQP_REPLAN_OFF_TRACK 2
+#define MPCQP_REPLAN_BLOCKED 3
+#define MPCQP_SWARM_MAP_MAX_LOOKAHEAD 64
+typedef struct mpcqp_swarm_map {
+  const uint8_t* grids;    /* T x rrt.height x rrt.width, row-major, 1 = free (inflated grids) */
+  int32_t num_grids;       /* T >= 1 */
+  int32_t epoch_steps;     /* >= 1: a vehicle that has taken k steps lives on grid min(k / epoch_steps, T - 1) */
+  int32_t lookahead;       /* 0..64 reference rows tested ahead of path_idx; 0: no blocked test */
+  int32_t reserved;
+  int32_t* grid_of;        /* V out/scratch: grid index of the vehicle's last trigger (read by the replanning) */
+  uint8_t* replan_cause;   /* V x max_replans out, nullable: MPCQP_REPLAN_ABORTED 1 / _OFF_TRACK 2 / _BLOCKED 3 */
+} mpcqp_swarm_map;
+
+int mpcqp_swarm_run_map(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s,
+                        const mpcqp_swarm_map* m, int steps, int use_graph, void* stream);
+int mpcqp_swarm_loop_map(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s,
+                         const mpcqp_swarm_map* m, void* stream);
 
 /*
  * Occupancy inflation: src/maps/inflate.py:18-51 (the fallback

@@ -172,6 +172,29 @@ __device__ __forceinline__ bool swarm_off_track(double x, double y, const double
 #pragma clang fp contract(off)
   return hypot(x - r[0], y - r[1]) > d;
 }
+// ---- the swarm on a changing map (mpcqp_swarm_loop_map / mpcqp_swarm_run_map), shared by k_swarm_loop_map
+// (mpcqp_solve.h) and k_swarm_trigger_map (mpcqp_swarm.hip): integer outcomes, the same in both.
+// grid(k) = min(k / epoch_steps, T - 1) of a vehicle that has taken k steps (a negative k, which no running
+// vehicle has, reads grid 0)
+__device__ __forceinline__ int swarm_map_index(const mpcqp::LoopMap& m, int k) {
+  return max(0, min(k / m.epoch_steps, m.num_grids - 1));
+}
+__device__ __forceinline__ const uint8_t* swarm_map_grid(const mpcqp::LoopMap& m, int k) {
+  return m.grids + (size_t)swarm_map_index(m, k) * m.height * m.width;
+}
+// is the cell of reference row r occupied?  The planner's own lookup (segment_free, mpcqp_plan.h): round
+// half to even, clipped to the grid
+__device__ __forceinline__ bool swarm_map_occupied(const mpcqp::LoopMap& m, const uint8_t* grid, const double* r) {
+  const int xi = (int)fmin(fmax(rint(r[0]), 0.0), (double)(m.width - 1));
+  const int yi = (int)fmin(fmax(rint(r[1]), 0.0), (double)(m.height - 1));
+  return grid[(size_t)yi * m.width + xi] == 0;
+}
+// a triggered vehicle's record (one thread): the grid its replan plans on, and why (MPCQP_REPLAN_*)
+__device__ __forceinline__ void swarm_map_note(const mpcqp::LoopMap& m, const mpcqp::LoopTrigger& tr, int v, int k,
+                                               int cause) {
+  m.grid_of[v] = swarm_map_index(m, k);
+  if (m.cause) m.cause[(size_t)v * tr.max_replans + tr.replans[v]] = (uint8_t)cause;
+}
 // goal test (control_stage.py:147-150)
 __device__ __forceinline__ bool fleet_at_goal(double x, double y, double gx, double gy) {
 #pragma clang fp contract(off)

@@ -585,9 +585,19 @@ struct ServeWarmLaunch {
   const int32_t* passes;  // device address of guess_passes (the block's last 8 bytes)
 };
 typedef void (*serve_warm_t)(hipStream_t, const mpcqp_params&, const ServeWarmLaunch&);
+// The changing map of mpcqp_swarm_loop_map (k_swarm_loop_map): the grids by epoch and the blocked test's
+// lookahead, with the grid size of the swarm's planner.  Not part of LoopTrigger: that struct is a by-value
+// argument of every loop kernel, and a field more would move all of their kernel-argument offsets.
+struct LoopMap {
+  const uint8_t* grids = nullptr;  // T x height x width, 1 = free
+  int num_grids = 0, epoch_steps = 1, lookahead = 0;
+  int width = 0, height = 0;
+  int32_t* grid_of = nullptr;      // V: the grid of the vehicle's last trigger
+  uint8_t* cause = nullptr;        // V x max_replans (nullable): MPCQP_REPLAN_*
+};
 // One fused-loop launch (device pointers), the loops' counterpart of Launch: k_fleet_loop (tr.pair: two
-// vehicles per wave), k_fleet_loop_mixed (cls != nullptr), k_fleet_loop_warm and k_swarm_loop_warm read what
-// they need of it.
+// vehicles per wave), k_fleet_loop_mixed (cls != nullptr), k_fleet_loop_warm, k_swarm_loop_warm and k_swarm_loop_map
+// (map) read what they need of it.
 struct LoopLaunch {
   const mpcqp_params* P;  // {nominal, relaxed}; with cls the 2 K interleaved blocks {nominal[c], relaxed[c]}
   const mpcqp_fleet* f;
@@ -602,6 +612,7 @@ struct LoopLaunch {
   int32_t* slots = nullptr;
   int guess_passes = 0;  // the warm loop's pass limit per attempt
   double* carry = nullptr;  // k_fleet_loop_warm_carry: the carried guess, V x 2 x N (nullable)
+  LoopMap map;  // k_swarm_loop_map only
 };
 typedef void (*fleet_loop_t)(hipStream_t, const LoopLaunch&);
 // The kernels of one horizon of the one-wave family (N < MPCQP_WIDE_MIN_HORIZON; the launch_*<N>
@@ -615,7 +626,8 @@ typedef void (*fleet_loop_t)(hipStream_t, const LoopLaunch&);
 // with the swarm's live replan trigger; two per wave where tr.pair), k_swarm_loop_mixed and
 // k_swarm_loop_mixed_warm (the swarm's cold and warm loops with a class per vehicle; never paired), and
 // k_solve_pair_mixed (a parameter block per QP, two QPs of one class per wave; nullptr above kPairMaxHorizon --
-// its loop counterpart k_fleet_loop_pair_mixed is launched by loop_mixed where L.slots is set).  The object that instantiates a
+// its loop counterpart k_fleet_loop_pair_mixed is launched by loop_mixed where L.slots is set), and k_swarm_loop_map
+// (the swarm's cold loop on a changing map, L.map; never paired).  The object that instantiates a
 // horizon registers it from a namespace-scope initialiser (register_horizons, mpcqp_solve.h: member by
 // member, since seven of them share one type); an all-null entry is a horizon not compiled in.
 struct HorizonKernels {
@@ -630,6 +642,7 @@ struct HorizonKernels {
   fleet_loop_t swarm_warm;
   fleet_loop_t swarm_mixed, swarm_mixed_warm;
   launcher_t pair_mixed;
+  fleet_loop_t swarm_map;  // k_swarm_loop_map: the cold swarm loop on a changing map (L.map); never paired
 };
 // fills entry N of the table in mpcqp.hip (constant-initialised, so the order of the objects'
 // initialisers does not matter)

@@ -2212,6 +2212,19 @@ struct CarryRow {
 template <>
 struct CarryRow<false> {};
 
+// SwarmMapWin: a vehicle of k_swarm_loop_map: FleetWin exactly; a type of its own for FleetCarryWin's reason.
+struct SwarmMapWin : FleetWin {};
+
+// The changing map of k_swarm_loop_map in fleet_loop_body: the grids by epoch, the lookahead of the blocked
+// test and the outputs of a trigger (grid_of, cause).  Handed in as CarryRow is: the loops without it carry
+// the empty one, so nothing of it reaches their code.
+template <bool Map>
+struct MapView {
+  mpcqp::LoopMap m;
+};
+template <>
+struct MapView<false> {};
+
 // ------------------------------------------------------------------ fused closed loop
 // Every vehicle of a fleet runs `steps` iterations of the loop body of TrajectoryTracker.track
 // (control_stage.py:100-150) on its own wave, with no kernel boundary between steps: the window
@@ -2237,13 +2250,19 @@ struct CarryRow<false> {};
 // cold loops never name it.
 // ColdWin: the window type of the cold solves, FleetWin for every loop but k_fleet_loop_pair_mixed (a type
 // per kernel family again).
+// Map (k_swarm_loop_map; cold, one vehicle per wave): after the off-track test the blocked test of the
+// changing map -- lane j < lookahead looks up row min(pidx + j, len - 1) of the reference in the grid of the
+// vehicle's step count, one whole-wave vote decides -- and every vehicle that leaves through to_replan
+// records the grid of its step count and its cause (swarm_map_note).
 template <int N, bool Pair, bool Warm = false, bool Carry = false,
-          class WarmWin = std::conditional_t<Carry, FleetCarryWin, FleetWin>, class ColdWin = FleetWin>
+          class WarmWin = std::conditional_t<Carry, FleetCarryWin, FleetWin>, class ColdWin = FleetWin,
+          bool Map = false>
 __device__ __forceinline__ void fleet_loop_body(const mpcqp_params* __restrict__ P, const mpcqp_fleet& f, int steps,
                                                 const mpcqp::LoopTrigger& tr, int b, int lane,
                                                 SolveLds<N, Pair>& sm, double* const ls, int guess_passes = 0,
-                                                CarryRow<Carry> carry = {}) {
+                                                CarryRow<Carry> carry = {}, MapView<Map> map = {}) {
   static_assert(Warm || !Carry, "the carried guess belongs to the warm loop");
+  static_assert(!Map || (!Pair && !Warm), "the changing map runs the cold loop at one vehicle per wave");
   using LN = Lanes<Pair>;
   const int V = f.vehicles;
   int phase = f.phase[b];
@@ -2262,7 +2281,12 @@ __device__ __forceinline__ void fleet_loop_body(const mpcqp_params* __restrict__
   if (phase != MPCQP_FLEET_RUNNING) {
     // an ABORTED vehicle with replans left is replanned before it steps again (the stepped swarm's
     // trigger fires for it in every step)
-    if (phase == MPCQP_FLEET_ABORTED && can_replan) to_replan(phase, f.state[(size_t)b * 4], f.state[(size_t)b * 4 + 1]);
+    if (phase == MPCQP_FLEET_ABORTED && can_replan) {
+      to_replan(phase, f.state[(size_t)b * 4], f.state[(size_t)b * 4 + 1]);
+      if constexpr (Map) {
+        if (lane == 0) swarm_map_note(map.m, tr, b, f.steps[b], MPCQP_REPLAN_ABORTED);
+      }
+    }
     return;
   }
   const int len = f.ref_len[b];
@@ -2275,6 +2299,7 @@ __device__ __forceinline__ void fleet_loop_body(const mpcqp_params* __restrict__
   // warm: the accepted solve's U of the step before, by lane; NaN (no step yet in this launch) is an
   // unusable guess, so a vehicle's first step is cold
   [[maybe_unused]] double Ug = __builtin_nan("");
+  [[maybe_unused]] int cause = MPCQP_REPLAN_OFF_TRACK;  // Map: why the vehicle left the step loop for a replan
   if constexpr (Carry) {  // the guess a launch before left; a row with a non-finite entry is unusable (solve_one)
     if (carry.rows && lane < 2 * N) Ug = carry.rows[(size_t)b * (2 * N) + lane];
   }
@@ -2374,6 +2399,17 @@ __device__ __forceinline__ void fleet_loop_body(const mpcqp_params* __restrict__
       phase = MPCQP_FLEET_REPLAN_RUNNING;
       break;
     }
+    if constexpr (Map) {  // the blocked test, where the off-track test did not fire: one row per lane, one vote
+      if (can_replan && map.m.lookahead > 0 && len >= 1 && len <= f.ref_stride && pidx >= 0 && pidx < len) {
+        const uint8_t* grid = swarm_map_grid(map.m, k);
+        const bool hit = lane < map.m.lookahead && swarm_map_occupied(map.m, grid, rows + (size_t)min(pidx + lane, len - 1) * 4);
+        if (LN::any(hit)) {
+          phase = MPCQP_FLEET_REPLAN_RUNNING;
+          cause = MPCQP_REPLAN_BLOCKED;
+          break;
+        }
+      }
+    }
   }
   if (lane < 4) f.state[(size_t)b * 4 + lane] = ls[lane];
   else if (lane < 6) f.u_prev[(size_t)b * 2 + lane - 4] = ls[lane];
@@ -2388,6 +2424,9 @@ __device__ __forceinline__ void fleet_loop_body(const mpcqp_params* __restrict__
   if ((phase == MPCQP_FLEET_ABORTED && can_replan) || phase == MPCQP_FLEET_REPLAN_RUNNING) {
     __syncthreads();
     to_replan(phase, ls[0], ls[1]);
+    if constexpr (Map) {
+      if (lane == 0) swarm_map_note(map.m, tr, b, k, phase == MPCQP_FLEET_ABORTED ? MPCQP_REPLAN_ABORTED : cause);
+    }
   }
 }
 
@@ -2625,6 +2664,25 @@ __global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_swarm_loop_mixed
                                                             guess_passes);
 }
 
+// ------------------------------------------------------------------ fused swarm loop on a changing map
+// mpcqp_swarm_loop_map: k_fleet_loop<N>'s dispatch (tr.order) and its live replan trigger around
+// fleet_loop_body's Map: the blocked test after the off-track test, and grid_of / replan_cause written by
+// every vehicle that leaves for a replan.  One vehicle per wave, cold.  The map is an argument of its own
+// (LoopTrigger stays what every other loop kernel takes).
+template <int N>
+__global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_swarm_loop_map(const mpcqp_params* __restrict__ P,
+                                                                             mpcqp_fleet f, int steps,
+                                                                             mpcqp::LoopTrigger tr,
+                                                                             mpcqp::LoopMap map) {
+  __shared__ SolveLds<N> sm;
+  __shared__ double ls[6];  // loop state: x[4], u_prev[2]
+  const int b = tr.order ? tr.order[blockIdx.x] : (int)blockIdx.x;
+  const int lane = (int)threadIdx.x;
+  if (b < 0 || b >= f.vehicles) return;
+  fleet_loop_body<N, false, false, false, FleetWin, SwarmMapWin, true>(P, f, steps, tr, b, lane, sm, ls, 0, {},
+                                                                       MapView<true>{map});
+}
+
 // ------------------------------------------------------------------ B = 1 server
 // One resident wave serving the sequential closed loop of TrajectoryTracker.track: it waits for the
 // host to raise box->req (system-scope loads of pinned host memory, s_sleep between polls), solves the
@@ -2812,6 +2870,11 @@ void launch_swarm_loop_mixed_warm(hipStream_t s, const LoopLaunch& L) {
   hipLaunchKernelGGL(k_swarm_loop_mixed_warm<N>, dim3(L.f->vehicles), dim3(kWave), 0, s, L.P, L.cls, L.K, *L.f,
                      L.steps, L.tr, L.guess_passes);
 }
+// the swarm's cold loop on a changing map (L.map) with the live trigger (L.tr); never paired
+template <int N>
+void launch_swarm_loop_map(hipStream_t s, const LoopLaunch& L) {
+  hipLaunchKernelGGL(k_swarm_loop_map<N>, dim3(L.f->vehicles), dim3(kWave), 0, s, L.P, *L.f, L.steps, L.tr, L.map);
+}
 // two QPs per wave from a caller's guess (N <= kPairMaxHorizon)
 template <int N>
 void launch_solve_pair_warm(hipStream_t s, const Launch& L) {
@@ -2853,6 +2916,7 @@ int register_horizons() {
   k.swarm_warm = &launch_swarm_loop_warm<LO>;
   k.swarm_mixed = &launch_swarm_loop_mixed<LO>;
   k.swarm_mixed_warm = &launch_swarm_loop_mixed_warm<LO>;
+  k.swarm_map = &launch_swarm_loop_map<LO>;
   if constexpr (LO <= kPairMaxHorizon) {
     k.pair = &launch_solve_pair<LO>;
     k.pair_warm = &launch_solve_pair_warm<LO>;

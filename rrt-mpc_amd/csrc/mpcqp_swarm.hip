@@ -24,6 +24,10 @@
 // k_swarm_loop_warm: each vehicle's solves start from its step before, cold at the first step of a launch.
 // mpcqp_swarm_loop_mixed / _mixed_warm are the same rounds again with a parameter class per vehicle
 // (k_swarm_loop_mixed, k_swarm_loop_mixed_warm); the replanning kernels read no parameter block.
+// mpcqp_swarm_run_map / mpcqp_swarm_loop_map are the stepped and the fused swarm on a map that changes with a
+// vehicle's step count: the trigger also fires for a reference that runs into a newly occupied cell
+// (k_swarm_trigger_map; inside the fused loop k_swarm_loop_map), and k_swarm_plan_map / k_swarm_paths_map plan on
+// the grid of the moment instead of s.occupancy.
 #include "mpcqp_build.h"
 #include "mpcqp_plan.h"
 #include "mpcqp_refbuild.h"
@@ -81,6 +85,65 @@ __global__ __launch_bounds__(kPlanThreads) void k_swarm_paths(mpcqp_fleet f, mpc
   const size_t M = (size_t)s.rrt.max_iterations + 2;
   rrt_extract_one(s.rrt, s.prune, s.occupancy, s.nodes + (size_t)v * M * 4, s.count + v, s.meta + 2 * (size_t)v,
                   s.raw + (size_t)v * M * 2, s.raw_len + v, s.pruned + (size_t)v * M * 2, s.pruned_len + v, lds, sm);
+}
+
+// ---- the stepped swarm on a changing map (mpcqp_swarm_run_map): k_swarm_trigger with the blocked test
+// after the off-track test (one thread per vehicle, the rows one after the other: the integer outcome of
+// k_swarm_loop_map's whole-wave vote), grid_of and the cause; k_swarm_plan / k_swarm_paths on the vehicle's grid.
+__global__ __launch_bounds__(kWave) void k_swarm_trigger_map(mpcqp_fleet f, mpcqp_swarm s, mpcqp::LoopMap m) {
+#pragma clang fp contract(off)
+  const int v = blockIdx.x * kWave + threadIdx.x;
+  if (v >= f.vehicles) return;
+  const int ph = f.phase[v];
+  const int used = s.replans[v];
+  if (used < 0 || used >= s.max_replans) return;
+  int cause = ph == MPCQP_FLEET_ABORTED ? MPCQP_REPLAN_ABORTED : 0;
+  if (ph == MPCQP_FLEET_RUNNING) {
+    const int len = f.ref_len[v], pi = f.path_idx[v];
+    if (len >= 1 && len <= f.ref_stride && pi >= 0 && pi < len) {
+      const double* rows = f.ref_global + (size_t)v * f.ref_stride * 4;
+      if (s.replan_distance > 0.0 &&
+          swarm_off_track(f.state[(size_t)v * 4], f.state[(size_t)v * 4 + 1], rows + (size_t)pi * 4, s.replan_distance)) {
+        cause = MPCQP_REPLAN_OFF_TRACK;
+      } else {
+        const uint8_t* grid = swarm_map_grid(m, f.steps[v]);
+        for (int j = 0; j < m.lookahead && !cause; ++j)
+          if (swarm_map_occupied(m, grid, rows + (size_t)min(pi + j, len - 1) * 4)) cause = MPCQP_REPLAN_BLOCKED;
+      }
+    }
+  }
+  if (!cause) return;
+  f.phase[v] = ph == MPCQP_FLEET_ABORTED ? MPCQP_FLEET_REPLAN_ABORTED : MPCQP_FLEET_REPLAN_RUNNING;
+  double* sg = s.start_goal + 4 * (size_t)v;
+  sg[0] = f.state[(size_t)v * 4];
+  sg[1] = f.state[(size_t)v * 4 + 1];
+  sg[2] = f.goal[(size_t)v * 2];
+  sg[3] = f.goal[(size_t)v * 2 + 1];
+  swarm_map_note(m, mpcqp::LoopTrigger{s.replan_distance, s.max_replans, s.replans, s.start_goal}, v, f.steps[v], cause);
+}
+
+__global__ __launch_bounds__(kPlanThreads) void k_swarm_plan_map(mpcqp_fleet f, mpcqp_swarm s, mpcqp::LoopMap m) {
+  extern __shared__ double lds[];
+  __shared__ PlanSmem sm;
+  const int v = blockIdx.x;
+  if (v >= f.vehicles || !replanning(f.phase[v])) return;
+  const int M = s.rrt.max_iterations + 2;
+  const uint64_t* rs = s.rng_table + ((size_t)v * s.max_replans + s.replans[v]) * 4;
+  const int g = max(0, min(m.grid_of[v], m.num_grids - 1));  // written by this launch sequence's trigger
+  rrt_grow_one(s.rrt, m.grids + (size_t)g * m.height * m.width, s.start_goal + 4 * (size_t)v, nullptr, rs,
+               s.nodes + (size_t)v * M * 4, s.count + v, s.meta + 2 * (size_t)v, lds, sm);
+}
+
+__global__ __launch_bounds__(kPlanThreads) void k_swarm_paths_map(mpcqp_fleet f, mpcqp_swarm s, mpcqp::LoopMap m) {
+  extern __shared__ double lds[];
+  __shared__ PlanSmem sm;
+  const int v = blockIdx.x;
+  if (v >= f.vehicles || !replanning(f.phase[v])) return;
+  const size_t M = (size_t)s.rrt.max_iterations + 2;
+  const int g = max(0, min(m.grid_of[v], m.num_grids - 1));
+  rrt_extract_one(s.rrt, s.prune, m.grids + (size_t)g * m.height * m.width, s.nodes + (size_t)v * M * 4, s.count + v,
+                  s.meta + 2 * (size_t)v, s.raw + (size_t)v * M * 2, s.raw_len + v, s.pruned + (size_t)v * M * 2,
+                  s.pruned_len + v, lds, sm);
 }
 
 // the planner's final path (rrt_star.py:264-283): smoothed when spline_samples > 1 and the
@@ -170,7 +233,8 @@ __global__ __launch_bounds__(kWave) void k_catmull_rom(int V, const double* __re
   if (threadIdx.x == 0) out_len[v] = k;
 }
 
-int check_swarm(const mpcqp_fleet* f, const mpcqp_swarm* s) {
+// need_occupancy == false: the calls on a changing map, which plan on their own grids
+int check_swarm(const mpcqp_fleet* f, const mpcqp_swarm* s, bool need_occupancy = true) {
   if (!s) return fail(MPCQP_E_ARG, "null swarm");
   if (s->max_replans < 0) return fail(MPCQP_E_ARG, "max_replans must be >= 0");
   if (s->rrt.max_iterations < 1 || s->rrt.max_iterations > kMaxPlanIterations)
@@ -180,12 +244,37 @@ int check_swarm(const mpcqp_fleet* f, const mpcqp_swarm* s) {
   if (s->horizon < 1 || s->horizon > MPCQP_MAX_HORIZON) return fail(MPCQP_E_HORIZON, "bad swarm horizon");
   if (!(s->dt > 0.0) || !(s->desired_speed > 0.0)) return fail(MPCQP_E_ARG, "dt and desired_speed must be > 0");
   if (s->max_replans > 0 &&
-      (!s->occupancy || !s->rng_table || !s->replans || !s->start_goal || !s->nodes || !s->count || !s->meta ||
+      ((need_occupancy && !s->occupancy) || !s->rng_table || !s->replans || !s->start_goal || !s->nodes || !s->count || !s->meta ||
        !s->raw || !s->raw_len || !s->pruned || !s->pruned_len || !s->smooth || !s->smooth_len || !s->new_ref ||
        !s->new_len))
     return fail(MPCQP_E_ARG, "null swarm buffer");
   (void)f;
   return MPCQP_OK;
+}
+
+// the map's own checks (after check_swarm: s is valid), and the device's view of it
+int check_map(const mpcqp_swarm* s, const mpcqp_swarm_map* m) {
+  if (!m) return fail(MPCQP_E_ARG, "null swarm map");
+  if (m->num_grids < 1) return fail(MPCQP_E_ARG, "num_grids must be >= 1");
+  if (m->epoch_steps < 1) return fail(MPCQP_E_ARG, "epoch_steps must be >= 1");
+  if (m->lookahead < 0 || m->lookahead > MPCQP_SWARM_MAP_MAX_LOOKAHEAD)
+    return fail(MPCQP_E_ARG, "lookahead outside [0, " + std::to_string(MPCQP_SWARM_MAP_MAX_LOOKAHEAD) + "]");
+  if (!m->grids) return fail(MPCQP_E_ARG, "null grids");
+  if (s->max_replans > 0 && !m->grid_of) return fail(MPCQP_E_ARG, "null grid_of");
+  return MPCQP_OK;
+}
+
+mpcqp::LoopMap loop_map(const mpcqp_swarm* s, const mpcqp_swarm_map* m) {
+  mpcqp::LoopMap d;
+  d.grids = m->grids;
+  d.num_grids = m->num_grids;
+  d.epoch_steps = m->epoch_steps;
+  d.lookahead = m->lookahead;
+  d.width = s->rrt.width;
+  d.height = s->rrt.height;
+  d.grid_of = m->grid_of;
+  d.cause = m->replan_cause;
+  return d;
 }
 
 size_t plan_lds(const mpcqp_rrt_params& p) {
@@ -202,13 +291,16 @@ struct ReplanLds {
 };
 
 // dynamic-LDS limits of the replanning kernels (outside any stream capture)
-int set_replan_attrs(const mpcqp_swarm* s) {
+int set_replan_attrs(const mpcqp_swarm* s, bool map = false) {
   const ReplanLds l(s);
   auto big = [](const void* k, size_t bytes) {
     return bytes > 65536 ? hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) : hipSuccess;
   };
-  hipError_t e = big(reinterpret_cast<const void*>(&k_swarm_plan), l.plan);
-  if (e == hipSuccess) e = big(reinterpret_cast<const void*>(&k_swarm_paths), l.paths);
+  hipError_t e = big(map ? reinterpret_cast<const void*>(&k_swarm_plan_map) : reinterpret_cast<const void*>(&k_swarm_plan),
+                     l.plan);
+  if (e == hipSuccess)
+    e = big(map ? reinterpret_cast<const void*>(&k_swarm_paths_map) : reinterpret_cast<const void*>(&k_swarm_paths),
+            l.paths);
   if (e == hipSuccess) e = big(reinterpret_cast<const void*>(&k_swarm_smooth), l.smooth);
   if (e == hipSuccess) e = big(reinterpret_cast<const void*>(&k_swarm_refbuild), l.refbuild);
   if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
@@ -216,16 +308,25 @@ int set_replan_attrs(const mpcqp_swarm* s) {
 }
 
 // trigger (unless the fused loop already flagged the vehicles) + the replanning kernels
-int enqueue_replan(const mpcqp_fleet* f, const mpcqp_swarm* s, hipStream_t st, bool trigger = true) {
+// m != nullptr (the calls on a changing map): the map's trigger, and the plan / paths kernels on each vehicle's grid
+int enqueue_replan(const mpcqp_fleet* f, const mpcqp_swarm* s, hipStream_t st, bool trigger = true,
+                   const mpcqp_swarm_map* m = nullptr) {
   const int V = f->vehicles;
   if (s->max_replans == 0 || V == 0) return MPCQP_OK;
   const mpcqp_fleet fv = *f;
   const mpcqp_swarm sv = *s;
   const ReplanLds l(s);
   const size_t lp = l.plan, lx = l.paths, lc = l.smooth, lr = l.refbuild;
-  if (trigger) hipLaunchKernelGGL(k_swarm_trigger, dim3((V + kWave - 1) / kWave), dim3(kWave), 0, st, fv, sv);
-  hipLaunchKernelGGL(k_swarm_plan, dim3(V), dim3(kPlanThreads), lp, st, fv, sv);
-  hipLaunchKernelGGL(k_swarm_paths, dim3(V), dim3(kPlanThreads), lx, st, fv, sv);
+  if (m) {
+    const mpcqp::LoopMap mv = loop_map(s, m);
+    if (trigger) hipLaunchKernelGGL(k_swarm_trigger_map, dim3((V + kWave - 1) / kWave), dim3(kWave), 0, st, fv, sv, mv);
+    hipLaunchKernelGGL(k_swarm_plan_map, dim3(V), dim3(kPlanThreads), lp, st, fv, sv, mv);
+    hipLaunchKernelGGL(k_swarm_paths_map, dim3(V), dim3(kPlanThreads), lx, st, fv, sv, mv);
+  } else {
+    if (trigger) hipLaunchKernelGGL(k_swarm_trigger, dim3((V + kWave - 1) / kWave), dim3(kWave), 0, st, fv, sv);
+    hipLaunchKernelGGL(k_swarm_plan, dim3(V), dim3(kPlanThreads), lp, st, fv, sv);
+    hipLaunchKernelGGL(k_swarm_paths, dim3(V), dim3(kPlanThreads), lx, st, fv, sv);
+  }
   hipLaunchKernelGGL(k_swarm_smooth, dim3(V), dim3(kWave), lc, st, fv, sv);
   hipLaunchKernelGGL(k_swarm_refbuild, dim3(V), dim3(kWave), lr, st, fv, sv);
   hipLaunchKernelGGL(k_swarm_commit, dim3(V), dim3(kWave), 0, st, fv, sv);
@@ -369,6 +470,71 @@ int mpcqp_swarm_run(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, 
         return attrs != MPCQP_OK ? attrs : mpcqp::fleet_buffers(nominal, relaxed, user);
       },
       [&](hipStream_t s2) { return mpcqp_swarm_step(nominal, relaxed, f, s, s2); });
+}
+
+// mpcqp_swarm_step on a changing map, after the swarm's and the map's checks: the fleet step, then the map's
+// trigger and the replanning on each flagged vehicle's grid
+static int swarm_step_map(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s,
+                          const mpcqp_swarm_map* m, void* stream) {
+  int rc = mpcqp_fleet_step(nominal, relaxed, f, stream);
+  if (rc) return rc;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) {
+    rc = set_replan_attrs(s, true);
+    if (rc) return rc;
+  }
+  return enqueue_replan(f, s, st, true, m);
+}
+
+int mpcqp_swarm_run_map(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s,
+                        const mpcqp_swarm_map* m, int steps, int use_graph, void* stream) {
+  int rc = check_swarm(f, s, false);
+  if (rc) return rc;
+  if ((rc = check_map(s, m)) != MPCQP_OK) return rc;
+  if (steps < 0) return fail(MPCQP_E_ARG, "steps must be >= 0");
+  if (!f || f->vehicles == 0 || steps == 0) return mpcqp_fleet_run(nominal, relaxed, f, 0, 0, stream);
+  hipStream_t user = static_cast<hipStream_t>(stream);
+  if (!use_graph) {
+    for (int i = 0; i < steps; ++i) {
+      rc = swarm_step_map(nominal, relaxed, f, s, m, stream);
+      if (rc) return rc;
+    }
+    return MPCQP_OK;
+  }
+  if ((rc = mpcqp_fleet_run(nominal, relaxed, f, 0, 0, stream)) != MPCQP_OK) return rc;  // the fleet's checks
+  return mpcqp::replay_graph(
+      "swarm map", user, steps,
+      [&] {
+        const int attrs = set_replan_attrs(s, true);
+        return attrs != MPCQP_OK ? attrs : mpcqp::fleet_buffers(nominal, relaxed, user);
+      },
+      [&](hipStream_t s2) { return swarm_step_map(nominal, relaxed, f, s, m, s2); });
+}
+
+// mpcqp_swarm_loop on a changing map: the same rounds with k_swarm_loop_map (the blocked test inside the
+// loop) and the replanning on each flagged vehicle's grid; one vehicle per wave, cold, no classes
+int mpcqp_swarm_loop_map(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s,
+                         const mpcqp_swarm_map* m, void* stream) {
+  int rc = check_swarm(f, s, false);
+  if (rc) return rc;
+  if ((rc = check_map(s, m)) != MPCQP_OK) return rc;
+  rc = mpcqp_fleet_loop(nominal, relaxed, f, 0, stream);  // the fleet's checks (no work at 0 steps)
+  if (rc) return rc;
+  const mpcqp::fleet_loop_t loop = mpcqp::fused_loop(nominal, relaxed, &mpcqp::HorizonKernels::swarm_map);
+  if (f->vehicles == 0) return MPCQP_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (s->max_replans > 0 && (rc = set_replan_attrs(s, true)) != MPCQP_OK) return rc;
+  if (!loop)  // mid / long horizons, reproducible or debug mode: the stepped swarm to the end
+    return mpcqp_swarm_run_map(nominal, relaxed, f, s, m, f->max_steps, 1, stream);
+  mpcqp::LoopLaunch L{nullptr, f, f->max_steps, {s->replan_distance, s->max_replans, s->replans, s->start_goal}};
+  L.map = loop_map(s, m);
+  for (int r = 0; r <= s->max_replans; ++r) {
+    rc = mpcqp::enqueue_fused_loop(nominal, relaxed, loop, "k_swarm_loop_map", MPCQP_LAUNCH_LOOP_MAP, false, L, st);
+    if (rc) return rc;
+    if (r < s->max_replans && (rc = enqueue_replan(f, s, st, false, m)) != MPCQP_OK) return rc;
+  }
+  return MPCQP_OK;
 }
 
 }  // extern "C"

@@ -43,11 +43,14 @@ PAIRING_MODES = {"off": PAIR_OFF, "on": PAIR_ON, "auto": PAIR_AUTO}
 E_DEVICE = -6  # MPCQP_E_DEVICE: a fault surfaced at a stream synchronisation
 # mpcqp_launch_info: info[0], the kind of the last solver launch recorded on a workspace (MPCQP_LAUNCH_*)
 (LAUNCH_NONE, LAUNCH_SOLVE, LAUNCH_SOLVE_MIXED, LAUNCH_SOLVE_WARM, LAUNCH_LOOP, LAUNCH_LOOP_MIXED, LAUNCH_LOOP_WARM,
- LAUNCH_LOOP_WARM_CARRY, LAUNCH_LOOP_MIXED_WARM) = range(9)
+ LAUNCH_LOOP_WARM_CARRY, LAUNCH_LOOP_MIXED_WARM, LAUNCH_LOOP_MAP) = range(10)
 LAUNCH_KINDS = {LAUNCH_NONE: "none", LAUNCH_SOLVE: "solve", LAUNCH_SOLVE_MIXED: "solve_mixed",
                 LAUNCH_SOLVE_WARM: "solve_warm", LAUNCH_LOOP: "loop", LAUNCH_LOOP_MIXED: "loop_mixed",
                 LAUNCH_LOOP_WARM: "loop_warm", LAUNCH_LOOP_WARM_CARRY: "loop_warm_carry",
-                LAUNCH_LOOP_MIXED_WARM: "loop_mixed_warm"}
+                LAUNCH_LOOP_MIXED_WARM: "loop_mixed_warm", LAUNCH_LOOP_MAP: "loop_map"}
+# mpcqp_swarm_map.replan_cause (MPCQP_REPLAN_*): why a vehicle of the swarm on a changing map replanned
+REPLAN_ABORTED, REPLAN_OFF_TRACK, REPLAN_BLOCKED = 1, 2, 3
+SWARM_MAP_MAX_LOOKAHEAD = 64  # MPCQP_SWARM_MAP_MAX_LOOKAHEAD
 # warm start (mpcqp_solve_warm, mpcqp_fleet_loop_warm): polish passes the guess's attempt may take
 DEFAULT_GUESS_PASSES = 8  # the best of 1, 2, 3, 5, 8 at 4096 vehicles, N = 20 (profiles/warm_start/)
 
@@ -266,6 +269,21 @@ class MpcqpSwarm(ctypes.Structure):
     ]
 
 
+class MpcqpSwarmMap(ctypes.Structure):
+    """``mpcqp_swarm_map`` (include/mpcqp.h): the grids by epoch and the blocked-path trigger of the swarm on a
+    changing map."""
+
+    _fields_ = [
+        ("grids", ctypes.c_void_p),
+        ("num_grids", ctypes.c_int32),
+        ("epoch_steps", ctypes.c_int32),
+        ("lookahead", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("grid_of", ctypes.c_void_p),
+        ("replan_cause", ctypes.c_void_p),
+    ]
+
+
 class LibraryError(RuntimeError):
     """A library call refused its arguments or failed to launch (mpcqp_* return code)."""
 
@@ -351,6 +369,10 @@ _SYMBOLS = {
     "mpcqp_swarm_loop_mixed_warm": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MpcqpFleet),
                                      ctypes.POINTER(MpcqpSwarm), ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p],
                                     ctypes.c_int),
+    "mpcqp_swarm_run_map": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MpcqpFleet), ctypes.POINTER(MpcqpSwarm),
+                             ctypes.POINTER(MpcqpSwarmMap), ctypes.c_int, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
+    "mpcqp_swarm_loop_map": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MpcqpFleet), ctypes.POINTER(MpcqpSwarm),
+                              ctypes.POINTER(MpcqpSwarmMap), ctypes.c_void_p], ctypes.c_int),
 }
 
 
@@ -417,6 +439,10 @@ __all__ = [
     "MpcqpFleet",
     "MpcqpRrtParams",
     "MpcqpSwarm",
+    "MpcqpSwarmMap",
+    "REPLAN_ABORTED",
+    "REPLAN_OFF_TRACK",
+    "REPLAN_BLOCKED",
     "RRT_MAX_ITERATIONS",
     "FLEET_REPLAN_RUNNING",
     "FLEET_REPLAN_ABORTED",

@@ -21,7 +21,11 @@ on the GPU with a per-step replan trigger.
                a replanned vehicle starts its new reference cold).  After
                ``Swarm.set_classes`` (``fused=True``): ``mpcqp_swarm_loop_mixed`` /
                ``mpcqp_swarm_loop_mixed_warm``, the same launches with a parameter class per vehicle
-               (``run(..., classes=)``).
+               (``run(..., classes=)``).  With ``grids=`` (a map that changes with time):
+               ``mpcqp_swarm_loop_map`` (``fused=True``) or ``mpcqp_swarm_run_map`` -- a vehicle that has
+               taken k steps lives on grid ``min(k // epoch_steps, T - 1)``, the trigger also fires when
+               one of the next ``lookahead`` reference rows lies on an occupied cell of that grid, and
+               the replanning plans on it.
 Every vehicle between replans follows the reference's single-vehicle loop exactly.
 """
 from __future__ import annotations
@@ -44,6 +48,37 @@ def replan_seed(seed: int, r: int) -> int:
     return int(seed) + REPLAN_SEED_STRIDE * (int(r) + 1)
 
 
+def grid_index(k, epoch_steps: int, num_grids: int):
+    """The grid a vehicle that has taken ``k`` steps lives on: ``min(k // epoch_steps, T - 1)`` (array or int)."""
+    return np.minimum(np.asarray(k) // int(epoch_steps), int(num_grids) - 1)
+
+
+def replan_grids(replans, replan_steps, epoch_steps: int, num_grids: int) -> np.ndarray:
+    """``(V, R)``: the grid each replan planned on -- ``grid_index`` of the step count recorded in
+    ``replan_steps`` (``steps`` where the replan gave a plan, ``-steps - 1`` where it failed) -- and -1 where no
+    replan happened."""
+    rs = np.asarray(replan_steps).astype(np.int64)
+    k = np.where(rs >= 0, rs, -rs - 1)
+    happened = np.arange(rs.shape[1])[None, :] < np.asarray(replans).reshape(-1, 1)
+    return np.where(happened, grid_index(k, epoch_steps, num_grids), -1).astype(np.int64)
+
+
+def map_hits(states, grids: np.ndarray, epoch_steps: int) -> np.ndarray:
+    """Per vehicle, the number of steps after which the vehicle's own cell (the planner's lookup: round half to
+    even, clipped) was occupied in the grid of that moment: ``states[v][i]`` is the state after step ``i + 1``."""
+    T, H, W = grids.shape
+    hits = np.zeros(len(states), dtype=np.int64)
+    for v, st in enumerate(states):
+        st = np.asarray(st, dtype=float).reshape(-1, 4)
+        if not len(st):
+            continue
+        g = grid_index(np.arange(1, len(st) + 1), epoch_steps, T)
+        xi = np.clip(np.rint(st[:, 0]), 0, W - 1).astype(np.int64)
+        yi = np.clip(np.rint(st[:, 1]), 0, H - 1).astype(np.int64)
+        hits[v] = int((grids[g, yi, xi] == 0).sum())
+    return hits
+
+
 @dataclass
 class SwarmResult:
     states: List[np.ndarray]  # per vehicle: states after each step, across replans
@@ -59,6 +94,10 @@ class SwarmResult:
     replan_over_capacity: Optional[np.ndarray] = None
     inputs: List[np.ndarray] = field(default_factory=list)  # per vehicle: applied u0 per step
     timings: Dict[str, float] = field(default_factory=dict)
+    # a swarm on a changing map (Swarm(grids=...)); None otherwise
+    replan_cause: Optional[np.ndarray] = None  # (V, max_replans): _lib.REPLAN_ABORTED / _OFF_TRACK / _BLOCKED, 0 unused
+    replan_grid: Optional[np.ndarray] = None  # (V, max_replans): the grid each replan planned on, -1 unused
+    hits: Optional[np.ndarray] = None  # (V,): steps after which the vehicle stood on an occupied cell of its grid
 
 
 class Swarm:
@@ -68,7 +107,8 @@ class Swarm:
     def __init__(self, occupancy: np.ndarray, mpc, planner: PlannerParameters, *, map_resolution: float,
                  max_vehicles: int, max_ref_len: int = 512, device=None, replan_distance: float = 15.0,
                  max_replans: int = 2, path_cap: int = 6144, use_graph: bool = True, fused: bool = False,
-                 warm_start: bool = False, guess_passes: Optional[int] = None, **settings) -> None:
+                 warm_start: bool = False, guess_passes: Optional[int] = None, grids: Optional[np.ndarray] = None,
+                 epoch_steps: Optional[int] = None, lookahead: int = 20, **settings) -> None:
         # warm start (mpcqp_swarm_loop_warm): opt-in, the fused swarm only.  Results equal the cold swarm's
         # to rounding, so a replanned vehicle's new plan may differ from the cold swarm's (RRT* decisions
         # sit on knife edges); guess_passes <= 0 is the cold swarm bit for bit.
@@ -76,6 +116,11 @@ class Swarm:
             raise ValueError("warm_start needs fused=True: only the fused swarm loop carries a guess from step to step")
         if guess_passes is not None and not warm_start:
             raise ValueError("guess_passes needs warm_start=True")
+        # a map that changes with time (mpcqp_swarm_loop_map / mpcqp_swarm_run_map): grids (T, H, W), grids[0] the
+        # grid the initial plans are made on; a vehicle that has taken k steps lives on grid
+        # min(k // epoch_steps, T - 1); lookahead: reference rows ahead of path_idx tested for occupied cells
+        self.grids, self.epoch_steps, self.lookahead = self._check_grids(occupancy, grids, epoch_steps, lookahead,
+                                                                         warm_start)
         self.warm_start = bool(warm_start)
         self.guess_passes = _lib.DEFAULT_GUESS_PASSES if guess_passes is None else int(guess_passes)
         # path_cap: smoothed points a replan may produce.  The default is the most that the device
@@ -98,6 +143,34 @@ class Swarm:
         self.fused = bool(fused)
         self._L = _lib.lib()
 
+    grids = None  # class defaults: a swarm on one grid
+    epoch_steps, lookahead = 1, 0
+
+    @staticmethod
+    def _check_grids(occupancy, grids, epoch_steps, lookahead, warm_start):
+        if grids is None:
+            if epoch_steps is not None:
+                raise ValueError("epoch_steps needs grids=")
+            return None, 1, 0
+        grids = np.ascontiguousarray(grids, dtype=np.uint8)
+        occupancy = np.asarray(occupancy)
+        if grids.ndim != 3 or grids.shape[0] < 1 or grids.shape[1:] != occupancy.shape:
+            raise ValueError(f"grids must have shape (T, {occupancy.shape[0]}, {occupancy.shape[1]}) with T >= 1, "
+                             f"got {grids.shape}")
+        if not np.array_equal(grids[0], occupancy):
+            raise ValueError("grids[0] must equal occupancy: the initial plans are made on it")
+        if warm_start:
+            raise ValueError("grids with warm_start=True: the changing map runs the cold swarm only")
+        if epoch_steps is None:
+            if grids.shape[0] > 1:
+                raise ValueError("grids with more than one grid need epoch_steps")
+            epoch_steps = 1
+        if int(epoch_steps) < 1:
+            raise ValueError(f"epoch_steps must be >= 1, got {epoch_steps}")
+        if not 0 <= int(lookahead) <= _lib.SWARM_MAP_MAX_LOOKAHEAD:
+            raise ValueError(f"lookahead must lie in [0, {_lib.SWARM_MAP_MAX_LOOKAHEAD}], got {lookahead}")
+        return grids, int(epoch_steps), int(lookahead)
+
     def set_classes(self, params_list, settings=None, relaxed_settings=None) -> None:
         """Per-vehicle parameter classes for the fused swarm (``mpcqp_swarm_loop_mixed``, with
         ``warm_start=True`` ``mpcqp_swarm_loop_mixed_warm``): block k of the nominal controller is
@@ -114,6 +187,8 @@ class Swarm:
             fleet.num_classes = 0
             fleet._class_params = None
             return
+        if self.grids is not None:
+            raise ValueError("set_classes on a swarm with grids: the changing map runs one parameter block")
         if not self.fused:
             raise ValueError("set_classes needs fused=True: only the fused swarm loop runs per-vehicle classes")
         if fleet.horizon > 32:
@@ -190,11 +265,26 @@ class Swarm:
         b["occupancy"] = occ
         return s, b
 
+    def _map_struct(self, V: int) -> tuple:
+        """``mpcqp_swarm_map`` of this swarm's grids and its device buffers (grids, grid_of, replan_cause)."""
+        torch = self.fleet._torch
+        n, R = max(V, 1), max(self.max_replans, 1)
+        b = {"grids": torch.from_numpy(self.grids).to(device=self.device),
+             "grid_of": torch.zeros((n,), dtype=torch.int32, device=self.device),
+             "replan_cause": torch.zeros((n, R), dtype=torch.uint8, device=self.device)}
+        m = _lib.MpcqpSwarmMap()
+        m.num_grids, m.epoch_steps, m.lookahead = int(self.grids.shape[0]), self.epoch_steps, self.lookahead
+        for k, t in b.items():
+            setattr(m, k, t.data_ptr())
+        return m, b
+
     def run(self, starts: np.ndarray, goals: np.ndarray, seeds=None, *, sim_steps: Optional[int] = None,
-            check_every: int = 10, classes=None) -> SwarmResult:
+            check_every: int = 10, classes=None, before_launch: Optional[Callable[[dict], None]] = None) -> SwarmResult:
         """``classes`` (int array or int32 device tensor, shape ``(V,)``; after ``set_classes``): vehicle
         v's block; an index outside the table aborts that vehicle with status ``BAD_CLASS`` and it never
-        replans.  Without ``classes`` a swarm with a table runs every vehicle under class 0."""
+        replans.  Without ``classes`` a swarm with a table runs every vehicle under class 0.
+        ``before_launch``: called with the fleet's buffers once the plans and references are on the device,
+        before the first launch (a replan overwrites a vehicle's reference rows; this is where to copy them)."""
         torch = self.fleet._torch
         starts = np.asarray(starts, dtype=float).reshape(-1, 2)
         goals = np.asarray(goals, dtype=float).reshape(-1, 2)
@@ -213,13 +303,22 @@ class Swarm:
         if (~planned).any():  # no plan: the vehicle never starts (the reference raises, :69-72)
             fb["phase"][torch.from_numpy(np.flatnonzero(~planned)).to(self.device)] = _lib.FLEET_ABORTED
         sw, sb = self._swarm_struct(V, seeds, planned)
+        on_map = self.grids is not None
+        if on_map and mixed:
+            raise ValueError("classes on a swarm with grids: the changing map runs one parameter block")
+        mp, mb = self._map_struct(V) if on_map else (None, None)
+        self._map_buffers = mb  # kept for inspection (grid_of)
+        if before_launch is not None:
+            before_launch(fb)
         torch.cuda.synchronize(self.device)
         t["refs_s"] = time.perf_counter() - t0
         t0 = time.perf_counter()
         stream = torch.cuda.current_stream(self.device)
         done = 0
         if self.fused and V:
-            if mixed:
+            if on_map:
+                call, args = "mpcqp_swarm_loop_map", (ctypes.byref(mp),)
+            elif mixed:
                 call = "mpcqp_swarm_loop_mixed_warm" if self.warm_start else "mpcqp_swarm_loop_mixed"
                 args = (fb["cls"].data_ptr(),) + ((self.guess_passes,) if self.warm_start else ())
             else:
@@ -231,10 +330,10 @@ class Swarm:
             done = total
         while done < total and V:
             k = min(check_every, total - done)
-            _lib.check(self._L.mpcqp_swarm_run(self.fleet._nominal._ws, self.fleet._relaxed._ws,
-                                               ctypes.byref(self.fleet._fleet), ctypes.byref(sw), int(k),
-                                               int(self.use_graph), ctypes.c_void_p(stream.cuda_stream)),
-                       "mpcqp_swarm_run")
+            call, args = ("mpcqp_swarm_run_map", (ctypes.byref(mp),)) if on_map else ("mpcqp_swarm_run", ())
+            _lib.check(getattr(self._L, call)(self.fleet._nominal._ws, self.fleet._relaxed._ws,
+                                              ctypes.byref(self.fleet._fleet), ctypes.byref(sw), *args, int(k),
+                                              int(self.use_graph), ctypes.c_void_p(stream.cuda_stream)), call)
             done += k
             if not bool((fb["phase"][:V] == _lib.FLEET_RUNNING).any().item()):
                 break
@@ -255,10 +354,16 @@ class Swarm:
                 last_paths.append(smooth[v, : sl[v]].copy())
             else:
                 last_paths.append(None)
+        extra = {}
+        if on_map:  # causes from the device; the grids of the replans and the hits are host arithmetic on the result
+            cause = mb["replan_cause"][:V, : max(self.max_replans, 1)].cpu().numpy()
+            extra = dict(replan_cause=np.where(np.arange(cause.shape[1])[None, :] < replans[:, None], cause, 0),
+                         replan_grid=replan_grids(replans, rsteps, self.epoch_steps, self.grids.shape[0]),
+                         hits=map_hits(r.states, self.grids, self.epoch_steps))
         return SwarmResult(states=r.states, phase=r.phase, steps=r.steps, replans=replans, planned=planned,
                            paths=found, replan_steps=rsteps, last_replan_start=sg[:, :2].copy(),
                            last_replan_path=last_paths, inputs=r.inputs, timings=t,
-                           replan_over_capacity=over_cap)
+                           replan_over_capacity=over_cap, **extra)
 
 
 # ------------------------------------------------------------------ multi-GPU: vehicles sharded over ranks
@@ -276,7 +381,7 @@ def shard_vehicles(V: int, world: int, rank: int) -> Tuple[int, int]:
 
 
 _PER_VEHICLE_ARRAYS = ("phase", "steps", "replans", "planned", "replan_steps", "last_replan_start",
-                       "replan_over_capacity")
+                       "replan_over_capacity", "replan_cause", "replan_grid", "hits")
 _PER_VEHICLE_LISTS = ("states", "paths", "last_replan_path", "inputs")
 
 
@@ -317,4 +422,4 @@ def run_swarm_sharded(run: Callable[..., SwarmResult], starts, goals, seeds, *, 
 
 
 __all__ = ["Swarm", "SwarmResult", "replan_seed", "REPLAN_SEED_STRIDE", "shard_vehicles", "merge_swarm_results",
-           "run_swarm_sharded"]
+           "run_swarm_sharded", "grid_index", "replan_grids", "map_hits"]

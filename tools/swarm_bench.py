@@ -15,6 +15,13 @@ mpcqp_swarm_loop_mixed_warm) against its K homogeneous sub-swarms run back to ba
 
     python tools/swarm_bench.py --classes 4 [--reps 15] [--guess-passes 8]
 
+The swarm on a changing map (Swarm(grids=...), mpcqp_swarm_loop_map): (a) the plain fused swarm against (b) the
+map swarm on an unchanged map (one grid, lookahead 20), interleaved -- what the blocked test costs -- and (c) the
+closing-passage map (the passage above the block closes after --epoch-steps steps), recorded alone: nothing could
+run it before.  The results kept under profiles/swarm_map/ come from this mode:
+
+    python tools/swarm_bench.py --map [--reps 15] [--epoch-steps 10] [--lookahead 20]
+
 Multi-GPU (BASELINE config 5 on 8 GPUs): vehicles sharded over ranks (mpcqp.pipeline.swarm
 .run_swarm_sharded), one process per GPU, the per-vehicle results gathered at the end:
 
@@ -242,6 +249,88 @@ def classes_bench(a) -> None:
     print(json.dumps(out))
 
 
+def map_bench(a) -> None:
+    """Legs (a) "plain": Swarm(fused=True), and (b) "map_static": the same swarm with grids = occ[None] and
+    --lookahead, on the same starts, goals and seeds: whole Swarm.run calls alternating within every repeat in one
+    process, the order rotating from repeat to repeat; repeat 0 warms up.  Then leg (c) "map_closing": grids =
+    [occ, occ with rows 2..33 of columns 36..40 occupied], --epoch-steps, timed the same way on its own.  Per leg:
+    medians with min and max of track_replan_s and of the end-to-end run, vehicle-steps, replans (by cause on the
+    map legs) and hits; (b) also says whether every vehicle did what it did in (a)."""
+    import torch
+
+    from mpcqp import _lib
+    from mpcqp.config import MPCConfig
+    from mpcqp.pipeline.swarm import Swarm
+    from mpcqp.planning.rrt_star import default_planner_parameters
+
+    occ = np.load(ROOT / "rrt-mpc_amd" / "mpcqp" / "data" / "default_plan.npz")["occupancy"]
+    closed = occ.copy()
+    closed[2:34, 36:41] = 0
+    prm = default_planner_parameters()
+    out = {"metric": "Swarm.run seconds: the plain fused swarm against the map swarm on an unchanged map, interleaved; "
+                     "the closing-passage map alone", "horizon": 15, "sim_steps": a.steps,
+           "replan_distance": a.replan_distance, "max_replans": a.max_replans, "lookahead": a.lookahead,
+           "epoch_steps": a.epoch_steps, "reps": a.reps, "runs": []}
+    mpc = MPCConfig(horizon=15, sim_steps=a.steps)
+
+    def timed(legs, starts, goals, V):
+        names = list(legs)
+        times = {k: {"track_replan_s": [], "end_to_end_s": []} for k in names}
+        res = {}
+        for r in range(a.reps + 1):  # repeat 0 warms up
+            for k in names[r % len(names):] + names[:r % len(names)]:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                res[k] = legs[k].run(starts, goals, seeds=np.arange(V))
+                torch.cuda.synchronize()
+                if r:
+                    times[k]["end_to_end_s"].append(time.perf_counter() - t0)
+                    times[k]["track_replan_s"].append(res[k].timings["track_replan_s"])
+        return res, times
+
+    def summary(sw, rk, ts, base=None):
+        info = sw.fleet._nominal.launch_info()
+        d = {"vehicle_steps": int(rk.steps.sum()), "goal_reached": int((rk.phase == 1).sum()),
+             "replans": int(rk.replans.sum()), "replans_with_new_plan": int((rk.replan_steps > 0).sum()),
+             "vehicles_replanned": int((rk.replans > 0).sum()), "launch": info["name"], "per_wave": info["per_wave"]}
+        if rk.replan_cause is not None:
+            d["replans_by_cause"] = {name: int((rk.replan_cause == code).sum()) for name, code in
+                                     (("aborted", _lib.REPLAN_ABORTED), ("off_track", _lib.REPLAN_OFF_TRACK),
+                                      ("blocked", _lib.REPLAN_BLOCKED))}
+            d["hits"] = {"vehicle_steps_on_an_occupied_cell": int(rk.hits.sum()), "vehicles": int((rk.hits > 0).sum())}
+        for what, t in ts.items():
+            med = float(np.median(t))
+            d[what] = {"median": med, "min": min(t), "max": max(t), "all": t}
+            if base is not None:
+                d[what]["over_plain"] = med / float(np.median(base[what]))
+        return d
+
+    for V in a.vehicles:
+        starts, goals = pairs(occ, V, 5)
+        kw = dict(map_resolution=0.8, max_vehicles=V, device="cuda:0", replan_distance=a.replan_distance,
+                  max_replans=a.max_replans, fused=True)
+        legs = {"plain": Swarm(occ, mpc, prm, **kw),
+                "map_static": Swarm(occ, mpc, prm, grids=occ[None], lookahead=a.lookahead, **kw)}
+        res, times = timed(legs, starts, goals, V)
+        run = {"vehicles": V, "planned": int(res["plain"].planned.sum()),
+               "plain": summary(legs["plain"], res["plain"], times["plain"]),
+               "map_static": summary(legs["map_static"], res["map_static"], times["map_static"], times["plain"])}
+        p, m = res["plain"], res["map_static"]
+        run["map_static"]["same_as_plain"] = bool(
+            np.array_equal(p.steps, m.steps) and np.array_equal(p.phase, m.phase)
+            and np.array_equal(p.replan_steps, m.replan_steps) and all(np.array_equal(x, y) for x, y in zip(p.states, m.states)))
+        for sw in legs.values():
+            sw.fleet.close()
+        closing = {"map_closing": Swarm(occ, mpc, prm, grids=np.stack([occ, closed]), epoch_steps=a.epoch_steps,
+                                        lookahead=a.lookahead, **kw)}
+        res, times = timed(closing, starts, goals, V)
+        run["map_closing"] = summary(closing["map_closing"], res["map_closing"], times["map_closing"])
+        closing["map_closing"].fleet.close()
+        out["runs"].append(run)
+        print(json.dumps(run), flush=True)
+    print(json.dumps(out))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--vehicles", type=int, nargs="+", default=[100, 1024])
@@ -263,7 +352,17 @@ def main() -> None:
     ap.add_argument("--classes", type=int, default=0,
                     help="K > 0: one mixed swarm of K parameter classes (mpcqp_swarm_loop_mixed[_warm]) against its K "
                          "homogeneous sub-swarms back to back, cold and warm, interleaved (--reps, --guess-passes)")
+    ap.add_argument("--map", action="store_true",
+                    help="the plain fused swarm against the map swarm on an unchanged map (mpcqp_swarm_loop_map), "
+                         "interleaved, and the closing-passage map alone (--reps, --epoch-steps, --lookahead)")
+    ap.add_argument("--epoch-steps", type=int, default=10, help="with --map: steps per grid of the closing-passage map")
+    ap.add_argument("--lookahead", type=int, default=20, help="with --map: reference rows the blocked test looks ahead")
     a = ap.parse_args()
+    if a.map:
+        if a.reps < 1:
+            ap.error("--reps must be >= 1")
+        map_bench(a)
+        return
     if a.classes:
         if a.reps < 1:
             ap.error("--reps must be >= 1")
