@@ -616,33 +616,26 @@ struct LoopLaunch {
 };
 typedef void (*fleet_loop_t)(hipStream_t, const LoopLaunch&);
 // The kernels of one horizon of the one-wave family (N < MPCQP_WIDE_MIN_HORIZON; the launch_*<N>
-// templates of mpcqp_solve.h): k_solve, k_solve_mixed (a parameter block per QP), k_solve_pair (two
-// QPs per wave, fused K1; nullptr above kPairMaxHorizon), k_serve (the B = 1 server), k_fleet_loop
-// (the fused closed loop), k_fleet_loop_mixed (the same with a class per vehicle), k_solve_warm (from a
-// caller's guess), k_fleet_loop_warm (the fused loop, each step from the one before) and k_serve_warm
-// (the B = 1 server from a caller's guess), k_solve_pair_warm (two QPs per wave from a caller's guess;
-// nullptr above kPairMaxHorizon) and k_fleet_loop_warm_carry (the warm loop with the guess carried across
-// launches; its launcher runs two vehicles per wave where tr.pair) and k_swarm_loop_warm (the warm loop
-// with the swarm's live replan trigger; two per wave where tr.pair), k_swarm_loop_mixed and
-// k_swarm_loop_mixed_warm (the swarm's cold and warm loops with a class per vehicle; never paired), and
-// k_solve_pair_mixed (a parameter block per QP, two QPs of one class per wave; nullptr above kPairMaxHorizon --
-// its loop counterpart k_fleet_loop_pair_mixed is launched by loop_mixed where L.slots is set), and k_swarm_loop_map
-// (the swarm's cold loop on a changing map, L.map; never paired).  The object that instantiates a
-// horizon registers it from a namespace-scope initialiser (register_horizons, mpcqp_solve.h: member by
-// member, since seven of them share one type); an all-null entry is a horizon not compiled in.
+// templates of mpcqp_solve.h), one member per launcher.  The object that instantiates a horizon registers
+// it from a namespace-scope initialiser (register_horizons, mpcqp_solve.h: member by member, since many
+// share one type); an all-null entry is a horizon not compiled in.
 struct HorizonKernels {
-  launcher_t solve, mixed, pair;
-  serve_t serve;
-  fleet_loop_t loop, loop_mixed;
-  launcher_t warm;
-  fleet_loop_t loop_warm;
-  serve_warm_t serve_warm;
-  launcher_t pair_warm;
-  fleet_loop_t loop_warm_carry;
-  fleet_loop_t swarm_warm;
-  fleet_loop_t swarm_mixed, swarm_mixed_warm;
-  launcher_t pair_mixed;
-  fleet_loop_t swarm_map;  // k_swarm_loop_map: the cold swarm loop on a changing map (L.map); never paired
+  launcher_t solve;               // k_solve
+  launcher_t mixed;               // k_solve_mixed: a parameter block per QP
+  launcher_t pair;                // k_solve_pair: two QPs per wave, fused K1; nullptr above kPairMaxHorizon
+  serve_t serve;                  // k_serve: the B = 1 server
+  fleet_loop_t loop;              // k_fleet_loop: the fused closed loop; two vehicles per wave where tr.pair
+  fleet_loop_t loop_mixed;        // k_fleet_loop_mixed: a class per vehicle; k_fleet_loop_pair_mixed where L.slots
+  launcher_t warm;                // k_solve_warm: from a caller's guess
+  fleet_loop_t loop_warm;         // k_fleet_loop_warm: the fused loop, each step from the one before
+  serve_warm_t serve_warm;        // k_serve_warm: the B = 1 server from a caller's guess
+  launcher_t pair_warm;           // k_solve_pair_warm: two QPs per wave from a guess; nullptr above kPairMaxHorizon
+  fleet_loop_t loop_warm_carry;   // k_fleet_loop_warm_carry: the guess carried across launches; tr.pair as loop
+  fleet_loop_t swarm_warm;        // k_swarm_loop_warm: the warm loop with the live replan trigger; tr.pair as loop
+  fleet_loop_t swarm_mixed;       // k_swarm_loop_mixed: the swarm's cold loop, a class per vehicle; never paired
+  fleet_loop_t swarm_mixed_warm;  // k_swarm_loop_mixed_warm: its warm loop; never paired
+  launcher_t pair_mixed;          // k_solve_pair_mixed: two QPs of one class per wave; nullptr above kPairMaxHorizon
+  fleet_loop_t swarm_map;         // k_swarm_loop_map: the swarm's cold loop on a changing map (L.map); never paired
 };
 // fills entry N of the table in mpcqp.hip (constant-initialised, so the order of the objects'
 // initialisers does not matter)

@@ -556,13 +556,36 @@ struct ServeWin {
   __device__ __forceinline__ int lane() const { return ln; }
 };
 
-// ClassWin: a mixed batch (k_solve_mixed): the caller's buffers exactly as BatchWin.  A type of its own
-// so that setup_qp / finish_qp are instantiated apart from k_solve's: helpers that two kernels share
-// are inlined differently, and the headline kernel's code generation stays what it was.
-struct ClassWin {
-  static constexpr bool kFleet = false;
-  __device__ __forceinline__ int lane() const { return threadIdx.x; }
+// A window type of its own for a kernel family: Base exactly, under another name, so that setup_qp,
+// solve_one and finish_qp are instantiated apart per family.  Helpers that two kernels share are inlined
+// differently in both, and the kernels that were there before (the headline k_solve first) would no longer
+// compile to what they were: seen with k_solve_mixed beside k_solve, k_serve_warm beside k_serve and
+// k_fleet_loop_warm_carry beside k_fleet_loop_warm, each at every horizon.  One enumerator and one alias
+// per family; a new family adds a line to each.
+enum class WinFamily {
+  kSolveMixed,
+  kSolveWarm,
+  kSolvePairMixed,
+  kSolvePairWarm,
+  kServeWarm,
+  kLoopWarmCarry,
+  kLoopPairMixed,
+  kSwarmWarm,
+  kSwarmMixedWarm,
+  kSwarmMap,
 };
+template <class Base, WinFamily Family>
+struct WinOf : Base {};
+using ClassWin = WinOf<BatchWin, WinFamily::kSolveMixed>;               // k_solve_mixed
+using GuessWin = WinOf<BatchWin, WinFamily::kSolveWarm>;                // k_solve_warm
+using PairClassWin = WinOf<ServeWin, WinFamily::kSolvePairMixed>;       // k_solve_pair_mixed
+using PairGuessWin = WinOf<ServeWin, WinFamily::kSolvePairWarm>;        // k_solve_pair_warm
+using ServeGuessWin = WinOf<ServeWin, WinFamily::kServeWarm>;           // k_serve_warm
+using FleetCarryWin = WinOf<FleetWin, WinFamily::kLoopWarmCarry>;       // k_fleet_loop_warm_carry
+using FleetClassPairWin = WinOf<FleetWin, WinFamily::kLoopPairMixed>;   // k_fleet_loop_pair_mixed
+using SwarmWarmWin = WinOf<FleetWin, WinFamily::kSwarmWarm>;            // k_swarm_loop_warm
+using SwarmMixedWarmWin = WinOf<FleetWin, WinFamily::kSwarmMixedWarm>;  // k_swarm_loop_mixed_warm
+using SwarmMapWin = WinOf<FleetWin, WinFamily::kSwarmMap>;              // k_swarm_loop_map
 
 // ------------------------------------------------------------------ K2 phase 1: setup
 // Condensing (states and slacks eliminated) + OSQP Ruiz/cost scaling.  Leaves the scaled
@@ -1721,13 +1744,6 @@ __device__ __forceinline__ int finish_qp(const mpcqp_params& p, int b, const dou
   return status;
 }
 
-// GuessWin: a batch with a caller's guess (k_solve_warm): the caller's buffers exactly as BatchWin; a
-// type of its own for ClassWin's reason.
-struct GuessWin {
-  static constexpr bool kFleet = false;
-  __device__ __forceinline__ int lane() const { return threadIdx.x; }
-};
-
 // A caller's guess in the solver's variables.  g: the lane's entry of a U in the output layout (lane
 // c N + k holds U[c][k]: accelerations on the speed lanes, steering angles after them); v0 = x0[3].  The
 // speeds v_{k+1} = v0 + dt sum_{j <= k} a_j (finish_qp's a_k = (v_{k+1} - v_k) / dt, inverted), the
@@ -2079,14 +2095,6 @@ __global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_solve_mixed(cons
                          U);
 }
 
-// PairClassWin: a QP of k_solve_pair_mixed: ServeWin exactly (the lane within the half, opaque); a type of
-// its own for ClassWin's reason.
-struct PairClassWin {
-  static constexpr bool kFleet = false;
-  int ln;
-  __device__ __forceinline__ int lane() const { return ln; }
-};
-
 // ------------------------------------------------------------------ K2, a parameter block per QP, two QPs per wave
 // A mixed batch under mpcqp_set_class_pairing (N <= 15): k_solve_pair's layout with the two QPs of a wave
 // taken from the slot table of k_class_slots (mpcqp_fleet.hip) instead of 2w and 2w + 1: half h of
@@ -2123,7 +2131,7 @@ __global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_solve_pair_mixed
   const int cw = __builtin_amdgcn_readfirstlane(c);
   const mpcqp_params p = P[cw];  // a copy, not a reference into the table: k_solve_mixed's reason
   double U;
-  solve_one<N, PairClassWin, true>(p, b, nullptr, in_x0, in_ref, in_up, PairClassWin{ln}, sm[h], u0o, Xo, Uo,
+  solve_one<N, PairClassWin, true>(p, b, nullptr, in_x0, in_ref, in_up, PairClassWin{{ln}}, sm[h], u0o, Xo, Uo,
                                    statuso, iterso, activeo, U);
 }
 
@@ -2150,14 +2158,6 @@ __global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_solve_warm(mpcqp
   solve_one<N, GuessWin, false, true>(p, b, nullptr, in_x0, in_ref, in_up, GuessWin{}, sm, u0o, Xo, Uo, statuso,
                                       iterso, activeo, U, Guess<true>{g, guess_passes});
 }
-
-// PairGuessWin: two QPs per wave from a caller's guess (k_solve_pair_warm): ServeWin exactly (the lane
-// within the half, opaque); a type of its own for ClassWin's reason.
-struct PairGuessWin {
-  static constexpr bool kFleet = false;
-  int ln;
-  __device__ __forceinline__ int lane() const { return ln; }
-};
 
 // ------------------------------------------------------------------ K2 from a caller's guess, two QPs per wave
 // mpcqp_solve_warm under MPCQP_PAIR_ON (N <= 15): k_solve_pair's layout (half h of workgroup w solves QP
@@ -2189,17 +2189,9 @@ __global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_solve_pair_warm(
   asm volatile("" : "+v"(ln));
   const double g = ln < 2 * N ? U_guess[(size_t)b * (2 * N) + ln] : 0.0;
   double U;
-  solve_one<N, PairGuessWin, true, true>(p, b, nullptr, in_x0, in_ref, in_up, PairGuessWin{ln}, sm[h], u0o, Xo, Uo,
+  solve_one<N, PairGuessWin, true, true>(p, b, nullptr, in_x0, in_ref, in_up, PairGuessWin{{ln}}, sm[h], u0o, Xo, Uo,
                                          statuso, iterso, activeo, U, Guess<true>{g, guess_passes});
 }
-
-// FleetCarryWin: a vehicle of k_fleet_loop_warm_carry: FleetWin exactly; a type of its own for ClassWin's
-// reason (solve_one's warm driver shared with k_fleet_loop_warm changed that kernel's code generation at
-// every horizon).
-struct FleetCarryWin : FleetWin {};
-
-// SwarmWarmWin: a vehicle of k_swarm_loop_warm: FleetWin exactly; a type of its own for the same reason.
-struct SwarmWarmWin : FleetWin {};
 
 // The carried guess of k_fleet_loop_warm_carry in fleet_loop_body: the V x 2 x N buffer (nullable) and
 // whether a solve of this launch was accepted.  The loops without it carry the empty one (no variable of
@@ -2211,9 +2203,6 @@ struct CarryRow {
 };
 template <>
 struct CarryRow<false> {};
-
-// SwarmMapWin: a vehicle of k_swarm_loop_map: FleetWin exactly; a type of its own for FleetCarryWin's reason.
-struct SwarmMapWin : FleetWin {};
 
 // The changing map of k_swarm_loop_map in fleet_loop_body: the grids by epoch, the lookahead of the blocked
 // test and the outputs of a trigger (grid_of, cause).  Handed in as CarryRow is: the loops without it carry
@@ -2246,17 +2235,12 @@ struct MapView<false> {};
 // the read inside the step loop) -- only if a solve of this launch was accepted.  Null rows: neither.
 // Warm with a live trigger (k_swarm_loop_warm): a vehicle that leaves through to_replan takes no guess
 // with it; paired, the other half of its wave goes on alone, as after a goal.
-// WarmWin: the window type of the warm solves (a type per kernel family, FleetCarryWin's reason); the
-// cold loops never name it.
-// ColdWin: the window type of the cold solves, FleetWin for every loop but k_fleet_loop_pair_mixed (a type
-// per kernel family again).
+// Win: the window type of the body's solves, FleetWin or the calling kernel family's own (WinOf).
 // Map (k_swarm_loop_map; cold, one vehicle per wave): after the off-track test the blocked test of the
 // changing map -- lane j < lookahead looks up row min(pidx + j, len - 1) of the reference in the grid of the
 // vehicle's step count, one whole-wave vote decides -- and every vehicle that leaves through to_replan
 // records the grid of its step count and its cause (swarm_map_note).
-template <int N, bool Pair, bool Warm = false, bool Carry = false,
-          class WarmWin = std::conditional_t<Carry, FleetCarryWin, FleetWin>, class ColdWin = FleetWin,
-          bool Map = false>
+template <int N, bool Pair, bool Warm = false, bool Carry = false, class Win = FleetWin, bool Map = false>
 __device__ __forceinline__ void fleet_loop_body(const mpcqp_params* __restrict__ P, const mpcqp_fleet& f, int steps,
                                                 const mpcqp::LoopTrigger& tr, int b, int lane,
                                                 SolveLds<N, Pair>& sm, double* const ls, int guess_passes = 0,
@@ -2324,33 +2308,18 @@ __device__ __forceinline__ void fleet_loop_body(const mpcqp_params* __restrict__
       const mpcqp_params& p = P[relax];  // P = {nominal, relaxed} in global memory (ws->dparams)
       FleetWin win{rows, ln, len, pidx, relax != 0, {ls[0], ls[1], ls[2], ls[3]}, {ls[4], ls[5]}};
       double Ul;
-      int st;
+      Guess<Warm> gs;
       if constexpr (Warm) {
         // the guess: the last U one step on (lane j <- j + 1 within each block, the last step repeated);
         // the nominal solve and the relaxed retry start from the same one
         double up = LN::shl1(Ug);
         asm volatile("" : "+v"(up));  // pinned: the shift runs on every lane, not inside the select below
-        const double g = (ln == N - 1 || ln == 2 * N - 1) ? Ug : up;
-        if constexpr (!std::is_same_v<WarmWin, FleetWin>) {
-          st = solve_one<N, WarmWin, Pair, true>(p, b, nullptr, nullptr, nullptr, nullptr, WarmWin{win}, sm,
-                                                 f.u0 + (size_t)relax * V * 2, f.X, nullptr,
-                                                 f.status + (size_t)relax * V, nullptr, nullptr, Ul,
-                                                 Guess<true>{g, guess_passes});
-        } else {
-          st = solve_one<N, FleetWin, Pair, true>(p, b, nullptr, nullptr, nullptr, nullptr, win, sm,
-                                                  f.u0 + (size_t)relax * V * 2, f.X, nullptr,
-                                                  f.status + (size_t)relax * V, nullptr, nullptr, Ul,
-                                                  Guess<true>{g, guess_passes});
-        }
-      } else if constexpr (!std::is_same_v<ColdWin, FleetWin>) {
-        st = solve_one<N, ColdWin, Pair>(p, b, nullptr, nullptr, nullptr, nullptr, ColdWin{win}, sm,
-                                         f.u0 + (size_t)relax * V * 2, f.X, nullptr,
-                                         f.status + (size_t)relax * V, nullptr, nullptr, Ul);
-      } else {
-        st = solve_one<N, FleetWin, Pair>(p, b, nullptr, nullptr, nullptr, nullptr, win, sm,
-                                          f.u0 + (size_t)relax * V * 2, f.X, nullptr,
-                                          f.status + (size_t)relax * V, nullptr, nullptr, Ul);
+        gs.lane = (ln == N - 1 || ln == 2 * N - 1) ? Ug : up;
+        gs.passes = guess_passes;
       }
+      const int st = solve_one<N, Win, Pair, Warm>(p, b, nullptr, nullptr, nullptr, nullptr, Win{win}, sm,
+                                                   f.u0 + (size_t)relax * V * 2, f.X, nullptr,
+                                                   f.status + (size_t)relax * V, nullptr, nullptr, Ul, gs);
       __syncthreads();  // the next solve (or step) reuses the LDS
       if (lane == 0) f.mask[(size_t)relax * V + b] = 1;
       if (st == MPCQP_SOLVED || st == MPCQP_SOLVED_INACCURATE) {
@@ -2483,10 +2452,6 @@ __global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_fleet_loop_mixed
   fleet_loop_body<N, false>(P + 2 * (size_t)c, f, steps, off, b, lane, sm, ls);
 }
 
-// FleetClassPairWin: a vehicle of k_fleet_loop_pair_mixed: FleetWin exactly; a type of its own for
-// FleetCarryWin's reason.
-struct FleetClassPairWin : FleetWin {};
-
 // ------------------------------------------------------------------ fused closed loop, a class per vehicle, two per wave
 // mpcqp_fleet_loop_mixed under mpcqp_set_class_pairing (N <= 15): k_fleet_loop_mixed's dispatch per half
 // around fleet_loop_body<N, true> on P + 2c, with the dead trigger.  Half h of workgroup w runs vehicle
@@ -2524,8 +2489,7 @@ __global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_fleet_loop_pair_
   }
   const int cw = __builtin_amdgcn_readfirstlane(c);  // one class per wave (the slot table's contract)
   const mpcqp::LoopTrigger off{0.0, 0, nullptr, nullptr};
-  fleet_loop_body<N, true, false, false, FleetWin, FleetClassPairWin>(P + 2 * (size_t)cw, f, steps, off, b, lane, sm,
-                                                                      ls);
+  fleet_loop_body<N, true, false, false, FleetClassPairWin>(P + 2 * (size_t)cw, f, steps, off, b, lane, sm, ls);
 }
 
 // ------------------------------------------------------------------ fused closed loop, warm started
@@ -2568,7 +2532,8 @@ __global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_fleet_loop_warm_
   const int lane = Pair ? (int)(threadIdx.x & 31) : (int)threadIdx.x;
   if (b < 0 || b >= f.vehicles) return;
   const mpcqp::LoopTrigger off{0.0, 0, nullptr, nullptr};
-  fleet_loop_body<N, Pair, true, true>(P, f, steps, off, b, lane, sm, ls, guess_passes, CarryRow<true>{U_carry});
+  fleet_loop_body<N, Pair, true, true, FleetCarryWin>(P, f, steps, off, b, lane, sm, ls, guess_passes,
+                                                      CarryRow<true>{U_carry});
 }
 
 // ------------------------------------------------------------------ fused swarm loop, warm started
@@ -2643,10 +2608,6 @@ __global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_swarm_loop_mixed
   fleet_loop_body<N, false>(P + 2 * (size_t)c, f, steps, tr, b, lane, sm, ls);
 }
 
-// SwarmMixedWarmWin: a vehicle of k_swarm_loop_mixed_warm: FleetWin exactly; a type of its own for
-// FleetCarryWin's reason.
-struct SwarmMixedWarmWin : FleetWin {};
-
 // mpcqp_swarm_loop_mixed_warm: the same dispatch around fleet_loop_body's Warm.  Ug starts as NaN in every
 // launch, as in k_swarm_loop_warm (a relaunched vehicle has a new reference).
 template <int N>
@@ -2679,8 +2640,8 @@ __global__ __launch_bounds__(kWave, kSolveWavesPerEU<N>) void k_swarm_loop_map(c
   const int b = tr.order ? tr.order[blockIdx.x] : (int)blockIdx.x;
   const int lane = (int)threadIdx.x;
   if (b < 0 || b >= f.vehicles) return;
-  fleet_loop_body<N, false, false, false, FleetWin, SwarmMapWin, true>(P, f, steps, tr, b, lane, sm, ls, 0, {},
-                                                                       MapView<true>{map});
+  fleet_loop_body<N, false, false, false, SwarmMapWin, true>(P, f, steps, tr, b, lane, sm, ls, 0, {},
+                                                             MapView<true>{map});
 }
 
 // ------------------------------------------------------------------ B = 1 server
@@ -2724,15 +2685,6 @@ __global__ __launch_bounds__(kWave, 1) void k_serve(mpcqp_params p, mpcqp::Serve
   }
 }
 
-// ServeGuessWin: the B = 1 server from a caller's guess (k_serve_warm): ServeWin exactly; a type of its
-// own for ClassWin's reason (setup_qp / finish_qp shared with k_serve changed k_serve's code generation
-// at every horizon).
-struct ServeGuessWin {
-  static constexpr bool kFleet = false;
-  int ln;
-  __device__ __forceinline__ int lane() const { return ln; }
-};
-
 // The B = 1 server from a caller's guess (mpcqp_solve_served_warm): k_serve's loop, each request through
 // solve_one's warm driver under mpcqp_solve_warm's contract.  W.guess: 2 x N doubles in the layout of the U
 // output, W.passes: the request's guess_passes; both in mapped host memory, written by the host before
@@ -2764,7 +2716,7 @@ __global__ __launch_bounds__(kWave, 1) void k_serve_warm(mpcqp_params p, mpcqp::
     const double* in = L.in;
     uint8_t* o = L.out;
     double Ul;
-    solve_one<N, ServeGuessWin, false, true>(p, 0, nullptr, in, in + 4, in + 4 + 4 * (N + 1), ServeGuessWin{ln}, sm,
+    solve_one<N, ServeGuessWin, false, true>(p, 0, nullptr, in, in + 4, in + 4 + 4 * (N + 1), ServeGuessWin{{ln}}, sm,
                                         reinterpret_cast<double*>(o + L.off[0]), reinterpret_cast<double*>(o + L.off[1]),
                                         reinterpret_cast<double*>(o + L.off[2]), reinterpret_cast<int32_t*>(o + L.off[3]),
                                         reinterpret_cast<int32_t*>(o + L.off[4]), o + L.off[5], Ul, Guess<true>{g, passes});
@@ -2797,16 +2749,24 @@ void launch_solve_mixed(hipStream_t s, const Launch& L) {
   hipLaunchKernelGGL(k_solve_mixed<N>, dim3(L.B), dim3(kWave), 0, s, L.table, L.cls, L.K, L.B, L.x0, L.ref, L.u_prev,
                      L.u0, L.X, L.U, L.st, L.it, L.ac);
 }
-template <int N>
-void launch_fleet_loop(hipStream_t s, const LoopLaunch& L) {
-  const mpcqp_fleet& f = *L.f;
-  if constexpr (2 * N <= 30) {
+// A loop kernel that has a two-per-wave form: two vehicles per wave on the (V + 1) / 2 grid where the
+// launch asks for it (L.tr.pair) and the horizon fits a half-wave, else one per wave.  kernel(pair): the
+// kernel's <N, pair> instance (a generic lambda, so the paired one exists for N <= kPairMaxHorizon only).
+template <int N, class Kernel, class... Args>
+void launch_pair_or_single(hipStream_t s, const LoopLaunch& L, Kernel kernel, const Args&... args) {
+  const int V = L.f->vehicles;
+  if constexpr (N <= kPairMaxHorizon) {
     if (L.tr.pair) {
-      hipLaunchKernelGGL((k_fleet_loop<N, true>), dim3((f.vehicles + 1) / 2), dim3(kWave), 0, s, L.P, f, L.steps, L.tr);
+      hipLaunchKernelGGL(kernel(std::true_type{}), dim3((V + 1) / 2), dim3(kWave), 0, s, args...);
       return;
     }
   }
-  hipLaunchKernelGGL(k_fleet_loop<N>, dim3(f.vehicles), dim3(kWave), 0, s, L.P, f, L.steps, L.tr);
+  hipLaunchKernelGGL(kernel(std::false_type{}), dim3(V), dim3(kWave), 0, s, args...);
+}
+template <int N>
+void launch_fleet_loop(hipStream_t s, const LoopLaunch& L) {
+  launch_pair_or_single<N>(
+      s, L, [](auto pair) { return &k_fleet_loop<N, decltype(pair)::value>; }, L.P, *L.f, L.steps, L.tr);
 }
 template <int N>
 void launch_fleet_loop_mixed(hipStream_t s, const LoopLaunch& L) {
@@ -2834,30 +2794,16 @@ void launch_fleet_loop_warm(hipStream_t s, const LoopLaunch& L) {
 // the warm loop with the carried guess (L.carry, nullable); L.tr.pair: two vehicles per wave
 template <int N>
 void launch_fleet_loop_warm_carry(hipStream_t s, const LoopLaunch& L) {
-  const mpcqp_fleet& f = *L.f;
-  if constexpr (N <= kPairMaxHorizon) {
-    if (L.tr.pair) {
-      hipLaunchKernelGGL((k_fleet_loop_warm_carry<N, true>), dim3((f.vehicles + 1) / 2), dim3(kWave), 0, s, L.P, f,
-                         L.steps, L.guess_passes, L.tr.order, L.carry);
-      return;
-    }
-  }
-  hipLaunchKernelGGL((k_fleet_loop_warm_carry<N, false>), dim3(f.vehicles), dim3(kWave), 0, s, L.P, f, L.steps,
-                     L.guess_passes, L.tr.order, L.carry);
+  launch_pair_or_single<N>(
+      s, L, [](auto pair) { return &k_fleet_loop_warm_carry<N, decltype(pair)::value>; }, L.P, *L.f, L.steps,
+      L.guess_passes, L.tr.order, L.carry);
 }
 // the warm loop with the swarm's live trigger (L.tr); L.tr.pair: two vehicles per wave
 template <int N>
 void launch_swarm_loop_warm(hipStream_t s, const LoopLaunch& L) {
-  const mpcqp_fleet& f = *L.f;
-  if constexpr (N <= kPairMaxHorizon) {
-    if (L.tr.pair) {
-      hipLaunchKernelGGL((k_swarm_loop_warm<N, true>), dim3((f.vehicles + 1) / 2), dim3(kWave), 0, s, L.P, f, L.steps,
-                         L.tr, L.guess_passes);
-      return;
-    }
-  }
-  hipLaunchKernelGGL((k_swarm_loop_warm<N, false>), dim3(f.vehicles), dim3(kWave), 0, s, L.P, f, L.steps, L.tr,
-                     L.guess_passes);
+  launch_pair_or_single<N>(
+      s, L, [](auto pair) { return &k_swarm_loop_warm<N, decltype(pair)::value>; }, L.P, *L.f, L.steps, L.tr,
+      L.guess_passes);
 }
 // the swarm's loops with a class per vehicle (L.cls, L.K) and the live trigger (L.tr); never paired
 template <int N>

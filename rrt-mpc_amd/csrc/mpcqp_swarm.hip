@@ -90,6 +90,8 @@ __global__ __launch_bounds__(kPlanThreads) void k_swarm_paths(mpcqp_fleet f, mpc
 // ---- the stepped swarm on a changing map (mpcqp_swarm_run_map): k_swarm_trigger with the blocked test
 // after the off-track test (one thread per vehicle, the rows one after the other: the integer outcome of
 // k_swarm_loop_map's whole-wave vote), grid_of and the cause; k_swarm_plan / k_swarm_paths on the vehicle's grid.
+// Twins of the three kernels above on purpose: a shared __device__ body changed the instructions of the kernels
+// on both sides, whichever way it took the map ("Fixed kernels").
 __global__ __launch_bounds__(kWave) void k_swarm_trigger_map(mpcqp_fleet f, mpcqp_swarm s, mpcqp::LoopMap m) {
 #pragma clang fp contract(off)
   const int v = blockIdx.x * kWave + threadIdx.x;
@@ -122,6 +124,12 @@ __global__ __launch_bounds__(kWave) void k_swarm_trigger_map(mpcqp_fleet f, mpcq
   swarm_map_note(m, mpcqp::LoopTrigger{s.replan_distance, s.max_replans, s.replans, s.start_goal}, v, f.steps[v], cause);
 }
 
+// the grid a flagged vehicle plans on: that of its trigger (grid_of, written by this launch sequence's trigger)
+__device__ __forceinline__ const uint8_t* replan_grid(const mpcqp::LoopMap& m, int v) {
+  const int g = max(0, min(m.grid_of[v], m.num_grids - 1));
+  return m.grids + (size_t)g * m.height * m.width;
+}
+
 __global__ __launch_bounds__(kPlanThreads) void k_swarm_plan_map(mpcqp_fleet f, mpcqp_swarm s, mpcqp::LoopMap m) {
   extern __shared__ double lds[];
   __shared__ PlanSmem sm;
@@ -129,8 +137,7 @@ __global__ __launch_bounds__(kPlanThreads) void k_swarm_plan_map(mpcqp_fleet f, 
   if (v >= f.vehicles || !replanning(f.phase[v])) return;
   const int M = s.rrt.max_iterations + 2;
   const uint64_t* rs = s.rng_table + ((size_t)v * s.max_replans + s.replans[v]) * 4;
-  const int g = max(0, min(m.grid_of[v], m.num_grids - 1));  // written by this launch sequence's trigger
-  rrt_grow_one(s.rrt, m.grids + (size_t)g * m.height * m.width, s.start_goal + 4 * (size_t)v, nullptr, rs,
+  rrt_grow_one(s.rrt, replan_grid(m, v), s.start_goal + 4 * (size_t)v, nullptr, rs,
                s.nodes + (size_t)v * M * 4, s.count + v, s.meta + 2 * (size_t)v, lds, sm);
 }
 
@@ -140,8 +147,7 @@ __global__ __launch_bounds__(kPlanThreads) void k_swarm_paths_map(mpcqp_fleet f,
   const int v = blockIdx.x;
   if (v >= f.vehicles || !replanning(f.phase[v])) return;
   const size_t M = (size_t)s.rrt.max_iterations + 2;
-  const int g = max(0, min(m.grid_of[v], m.num_grids - 1));
-  rrt_extract_one(s.rrt, s.prune, m.grids + (size_t)g * m.height * m.width, s.nodes + (size_t)v * M * 4, s.count + v,
+  rrt_extract_one(s.rrt, s.prune, replan_grid(m, v), s.nodes + (size_t)v * M * 4, s.count + v,
                   s.meta + 2 * (size_t)v, s.raw + (size_t)v * M * 2, s.raw_len + v, s.pruned + (size_t)v * M * 2,
                   s.pruned_len + v, lds, sm);
 }
@@ -290,17 +296,28 @@ struct ReplanLds {
         refbuild(sizeof(double) * 3 * (size_t)(s->path_cap < kRefCap ? s->path_cap : kRefCap)) {}
 };
 
+// The three replanning kernels that read the map, chosen once: those of the fixed map (s->occupancy), or
+// their _map twins for the calls on a changing map.  Launched through these handles with one argument
+// list (f, s, map), of which the fixed map's kernels take the first two.
+struct MapKernels {
+  const void *trigger, *plan, *paths;
+};
+MapKernels map_kernels(const mpcqp_swarm_map* m) {
+  using K = const void*;
+  return m ? MapKernels{(K)&k_swarm_trigger_map, (K)&k_swarm_plan_map, (K)&k_swarm_paths_map}
+           : MapKernels{(K)&k_swarm_trigger, (K)&k_swarm_plan, (K)&k_swarm_paths};
+}
+
 // dynamic-LDS limits of the replanning kernels (outside any stream capture)
-int set_replan_attrs(const mpcqp_swarm* s, bool map = false) {
+int set_replan_attrs(const mpcqp_swarm* s, const mpcqp_swarm_map* m) {
   const ReplanLds l(s);
-  auto big = [](const void* k, size_t bytes) {
-    return bytes > 65536 ? hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) : hipSuccess;
+  const MapKernels k = map_kernels(m);
+  auto big = [](const void* kernel, size_t bytes) {
+    return bytes > 65536 ? hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)
+                         : hipSuccess;
   };
-  hipError_t e = big(map ? reinterpret_cast<const void*>(&k_swarm_plan_map) : reinterpret_cast<const void*>(&k_swarm_plan),
-                     l.plan);
-  if (e == hipSuccess)
-    e = big(map ? reinterpret_cast<const void*>(&k_swarm_paths_map) : reinterpret_cast<const void*>(&k_swarm_paths),
-            l.paths);
+  hipError_t e = big(k.plan, l.plan);
+  if (e == hipSuccess) e = big(k.paths, l.paths);
   if (e == hipSuccess) e = big(reinterpret_cast<const void*>(&k_swarm_smooth), l.smooth);
   if (e == hipSuccess) e = big(reinterpret_cast<const void*>(&k_swarm_refbuild), l.refbuild);
   if (e != hipSuccess) return fail(MPCQP_E_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
@@ -309,28 +326,67 @@ int set_replan_attrs(const mpcqp_swarm* s, bool map = false) {
 
 // trigger (unless the fused loop already flagged the vehicles) + the replanning kernels
 // m != nullptr (the calls on a changing map): the map's trigger, and the plan / paths kernels on each vehicle's grid
-int enqueue_replan(const mpcqp_fleet* f, const mpcqp_swarm* s, hipStream_t st, bool trigger = true,
-                   const mpcqp_swarm_map* m = nullptr) {
+int enqueue_replan(const mpcqp_fleet* f, const mpcqp_swarm* s, const mpcqp_swarm_map* m, hipStream_t st,
+                   bool trigger = true) {
   const int V = f->vehicles;
   if (s->max_replans == 0 || V == 0) return MPCQP_OK;
-  const mpcqp_fleet fv = *f;
-  const mpcqp_swarm sv = *s;
+  mpcqp_fleet fv = *f;
+  mpcqp_swarm sv = *s;
+  mpcqp::LoopMap mv = m ? loop_map(s, m) : mpcqp::LoopMap{};
+  void* args[] = {&fv, &sv, &mv};  // a launch error shows in launched() below, as after <<<>>>
+  const MapKernels k = map_kernels(m);
   const ReplanLds l(s);
-  const size_t lp = l.plan, lx = l.paths, lc = l.smooth, lr = l.refbuild;
-  if (m) {
-    const mpcqp::LoopMap mv = loop_map(s, m);
-    if (trigger) hipLaunchKernelGGL(k_swarm_trigger_map, dim3((V + kWave - 1) / kWave), dim3(kWave), 0, st, fv, sv, mv);
-    hipLaunchKernelGGL(k_swarm_plan_map, dim3(V), dim3(kPlanThreads), lp, st, fv, sv, mv);
-    hipLaunchKernelGGL(k_swarm_paths_map, dim3(V), dim3(kPlanThreads), lx, st, fv, sv, mv);
-  } else {
-    if (trigger) hipLaunchKernelGGL(k_swarm_trigger, dim3((V + kWave - 1) / kWave), dim3(kWave), 0, st, fv, sv);
-    hipLaunchKernelGGL(k_swarm_plan, dim3(V), dim3(kPlanThreads), lp, st, fv, sv);
-    hipLaunchKernelGGL(k_swarm_paths, dim3(V), dim3(kPlanThreads), lx, st, fv, sv);
-  }
+  const size_t lc = l.smooth, lr = l.refbuild;
+  if (trigger) (void)hipLaunchKernel(k.trigger, dim3((V + kWave - 1) / kWave), dim3(kWave), args, 0, st);
+  (void)hipLaunchKernel(k.plan, dim3(V), dim3(kPlanThreads), args, l.plan, st);
+  (void)hipLaunchKernel(k.paths, dim3(V), dim3(kPlanThreads), args, l.paths, st);
   hipLaunchKernelGGL(k_swarm_smooth, dim3(V), dim3(kWave), lc, st, fv, sv);
   hipLaunchKernelGGL(k_swarm_refbuild, dim3(V), dim3(kWave), lr, st, fv, sv);
   hipLaunchKernelGGL(k_swarm_commit, dim3(V), dim3(kWave), 0, st, fv, sv);
   return mpcqp::launched("swarm replan");
+}
+
+// One closed-loop step after the caller's checks: the fleet step, then the trigger and the replanning (m: on the
+// changing map)
+int swarm_step(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s,
+               const mpcqp_swarm_map* m, void* stream) {
+  int rc = mpcqp_fleet_step(nominal, relaxed, f, stream);
+  if (rc) return rc;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) {
+    rc = set_replan_attrs(s, m);
+    if (rc) return rc;
+  }
+  return enqueue_replan(f, s, m, st);
+}
+
+// mpcqp_swarm_run (m == nullptr) and mpcqp_swarm_run_map: `steps` steps, one by one or as a replayed hipGraph.
+// map: the call is the map's (check_map refuses a null m); it plans on its own grids (no s->occupancy) and runs
+// the fleet's checks before the capture.
+int swarm_run(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s,
+              const mpcqp_swarm_map* m, bool map, int steps, int use_graph, void* stream) {
+  int rc = check_swarm(f, s, !map);
+  if (rc) return rc;
+  if (map && (rc = check_map(s, m)) != MPCQP_OK) return rc;
+  if (steps < 0) return fail(MPCQP_E_ARG, "steps must be >= 0");
+  if (!f || f->vehicles == 0 || steps == 0) return mpcqp_fleet_run(nominal, relaxed, f, 0, 0, stream);
+  hipStream_t user = static_cast<hipStream_t>(stream);
+  if (!use_graph) {
+    for (int i = 0; i < steps; ++i) {
+      rc = swarm_step(nominal, relaxed, f, s, m, stream);
+      if (rc) return rc;
+    }
+    return MPCQP_OK;
+  }
+  if (map && (rc = mpcqp_fleet_run(nominal, relaxed, f, 0, 0, stream)) != MPCQP_OK) return rc;  // the fleet's checks
+  return mpcqp::replay_graph(
+      map ? "swarm map" : "swarm", user, steps,
+      [&] {
+        const int attrs = set_replan_attrs(s, m);
+        return attrs != MPCQP_OK ? attrs : mpcqp::fleet_buffers(nominal, relaxed, user);
+      },
+      [&](hipStream_t s2) { return swarm_step(nominal, relaxed, f, s, m, s2); });
 }
 
 }  // namespace
@@ -355,36 +411,51 @@ int mpcqp_catmull_rom(int V, const double* in, const int32_t* in_len, int in_str
 }
 
 int mpcqp_swarm_step(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s, void* stream) {
-  int rc = check_swarm(f, s);
-  if (rc) return rc;
-  rc = mpcqp_fleet_step(nominal, relaxed, f, stream);
-  if (rc) return rc;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) {
-    rc = set_replan_attrs(s);
-    if (rc) return rc;
-  }
-  return enqueue_replan(f, s, st);
+  const int rc = check_swarm(f, s);
+  return rc ? rc : swarm_step(nominal, relaxed, f, s, nullptr, stream);
 }
 
-// mpcqp_swarm_loop (warm == false) and mpcqp_swarm_loop_warm after the swarm's and the fleet's checks:
-// max_replans + 1 rounds of the fused loop with the trigger inside -- every vehicle runs until it
-// triggers or ends, the flagged ones are replanned; a vehicle's r-th trigger comes in round r - 1, so
-// the last round triggers none.  Cold, a parameter block without the fused loop runs the stepped swarm
-// to the end; warm, it is refused before anything is enqueued or invalidated.
+int mpcqp_swarm_run(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s, int steps,
+                    int use_graph, void* stream) {
+  return swarm_run(nominal, relaxed, f, s, nullptr, false, steps, use_graph, stream);
+}
+
+int mpcqp_swarm_run_map(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s,
+                        const mpcqp_swarm_map* m, int steps, int use_graph, void* stream) {
+  return swarm_run(nominal, relaxed, f, s, m, true, steps, use_graph, stream);
+}
+
+// The five fused swarm calls after their own argument checks: max_replans + 1 rounds of the fused loop with
+// the trigger inside -- every vehicle runs until it triggers or ends, the flagged ones are replanned; a
+// vehicle's r-th trigger comes in round r - 1, so the last round triggers none.
+// Cold (mpcqp_swarm_loop, and mpcqp_swarm_loop_map), a parameter block without the fused loop runs the
+// stepped swarm to the end; warm, it is refused before anything is enqueued or invalidated.
 // mixed != nullptr (mpcqp_swarm_loop_mixed, mpcqp_swarm_loop_mixed_warm): the same rounds with a class per
 // vehicle (cls), k_swarm_loop_mixed / k_swarm_loop_mixed_warm under the two workspaces' class tables;
 // `mixed` names the caller in the refusals, and neither has a stepped fallback.
-static int swarm_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s, bool warm,
-                      int guess_passes, void* stream, const char* mixed = nullptr, const int32_t* cls = nullptr) {
-  int rc = check_swarm(f, s);
+// map (mpcqp_swarm_loop_map): k_swarm_loop_map (the blocked test inside the loop) and the replanning on each
+// flagged vehicle's grid; one vehicle per wave, cold, no classes.
+static int swarm_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s,
+                      const mpcqp_swarm_map* m, bool map, bool warm, int guess_passes, void* stream,
+                      const char* mixed = nullptr, const int32_t* cls = nullptr) {
+  using HK = mpcqp::HorizonKernels;
+  struct Variant {
+    mpcqp::fleet_loop_t HK::*member;
+    const char* name;
+    int kind;
+  };
+  const Variant var =
+      map ? Variant{&HK::swarm_map, "k_swarm_loop_map", MPCQP_LAUNCH_LOOP_MAP}
+      : mixed ? (warm ? Variant{&HK::swarm_mixed_warm, "k_swarm_loop_mixed_warm", MPCQP_LAUNCH_LOOP_MIXED_WARM}
+                      : Variant{&HK::swarm_mixed, "k_swarm_loop_mixed", MPCQP_LAUNCH_LOOP_MIXED})
+              : (warm ? Variant{&HK::swarm_warm, "k_swarm_loop_warm", MPCQP_LAUNCH_LOOP_WARM}
+                      : Variant{&HK::loop, "k_fleet_loop", MPCQP_LAUNCH_LOOP});
+  int rc = check_swarm(f, s, !map);
   if (rc) return rc;
+  if (map && (rc = check_map(s, m)) != MPCQP_OK) return rc;
   rc = mpcqp_fleet_loop(nominal, relaxed, f, 0, stream);  // the fleet's checks (no work at 0 steps)
   if (rc) return rc;
-  using HK = mpcqp::HorizonKernels;
-  const mpcqp::fleet_loop_t loop = mpcqp::fused_loop(
-      nominal, relaxed, mixed ? (warm ? &HK::swarm_mixed_warm : &HK::swarm_mixed) : (warm ? &HK::swarm_warm : &HK::loop));
+  const mpcqp::fleet_loop_t loop = mpcqp::fused_loop(nominal, relaxed, var.member);
   if (mixed && !loop)
     return fail(MPCQP_E_HORIZON, std::string(mixed) + " runs the fused one-wave loop only (N <= 32, fast mode, no "
                                                       "debug_state): the stepped swarm has no per-vehicle classes");
@@ -404,137 +475,52 @@ static int swarm_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f
   }
   if (f->vehicles == 0) return MPCQP_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (s->max_replans > 0 && (rc = set_replan_attrs(s)) != MPCQP_OK) return rc;
+  if (s->max_replans > 0 && (rc = set_replan_attrs(s, m)) != MPCQP_OK) return rc;
   if (!loop)  // mid / long horizons, reproducible or debug mode: the stepped swarm to the end
-    return mpcqp_swarm_run(nominal, relaxed, f, s, f->max_steps, 1, stream);
+    return swarm_run(nominal, relaxed, f, s, m, map, f->max_steps, 1, stream);
   if (mixed && (rc = mpcqp::grow_loop_classes(nominal, st)) != MPCQP_OK) return rc;
   mpcqp::LoopLaunch L{nullptr, f, f->max_steps, {s->replan_distance, s->max_replans, s->replans, s->start_goal}};
   if (warm) L.guess_passes = guess_passes;
+  if (map) L.map = loop_map(s, m);
   if (mixed) {
     L.cls = cls;
     L.K = nominal->n_classes;
   } else if (warm) {
     L.tr.pair = mpcqp::use_pairs_warm(nominal);
   }
-  const char* name = mixed ? (warm ? "k_swarm_loop_mixed_warm" : "k_swarm_loop_mixed")
-                           : (warm ? "k_swarm_loop_warm" : "k_fleet_loop");
-  const int kind = mixed ? (warm ? MPCQP_LAUNCH_LOOP_MIXED_WARM : MPCQP_LAUNCH_LOOP_MIXED)
-                         : (warm ? MPCQP_LAUNCH_LOOP_WARM : MPCQP_LAUNCH_LOOP);
   for (int r = 0; r <= s->max_replans; ++r) {
-    rc = mpcqp::enqueue_fused_loop(nominal, relaxed, loop, name, kind, !warm && !mixed, L, st);
+    rc = mpcqp::enqueue_fused_loop(nominal, relaxed, loop, var.name, var.kind, !warm && !mixed && !map, L, st);
     if (rc) return rc;
-    if (r < s->max_replans && (rc = enqueue_replan(f, s, st, false)) != MPCQP_OK) return rc;
+    if (r < s->max_replans && (rc = enqueue_replan(f, s, m, st, false)) != MPCQP_OK) return rc;
   }
   return MPCQP_OK;
 }
 
 int mpcqp_swarm_loop(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s, void* stream) {
-  return swarm_loop(nominal, relaxed, f, s, false, 0, stream);
+  return swarm_loop(nominal, relaxed, f, s, nullptr, false, false, 0, stream);
 }
 
 int mpcqp_swarm_loop_warm(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s,
                           int guess_passes, void* stream) {
-  return swarm_loop(nominal, relaxed, f, s, true, guess_passes, stream);
+  return swarm_loop(nominal, relaxed, f, s, nullptr, false, true, guess_passes, stream);
 }
 
 int mpcqp_swarm_loop_mixed(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s,
                            const int32_t* cls, void* stream) {
   if (!cls) return fail(MPCQP_E_ARG, "null cls");
-  return swarm_loop(nominal, relaxed, f, s, false, 0, stream, "mpcqp_swarm_loop_mixed", cls);
+  return swarm_loop(nominal, relaxed, f, s, nullptr, false, false, 0, stream, "mpcqp_swarm_loop_mixed", cls);
 }
 
 int mpcqp_swarm_loop_mixed_warm(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s,
                                 const int32_t* cls, int guess_passes, void* stream) {
   if (!cls) return fail(MPCQP_E_ARG, "null cls");
-  return swarm_loop(nominal, relaxed, f, s, true, guess_passes, stream, "mpcqp_swarm_loop_mixed_warm", cls);
+  return swarm_loop(nominal, relaxed, f, s, nullptr, false, true, guess_passes, stream, "mpcqp_swarm_loop_mixed_warm",
+                    cls);
 }
 
-int mpcqp_swarm_run(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s, int steps,
-                    int use_graph, void* stream) {
-  int rc = check_swarm(f, s);
-  if (rc) return rc;
-  if (steps < 0) return fail(MPCQP_E_ARG, "steps must be >= 0");
-  if (!f || f->vehicles == 0 || steps == 0) return mpcqp_fleet_run(nominal, relaxed, f, 0, 0, stream);
-  hipStream_t user = static_cast<hipStream_t>(stream);
-  if (!use_graph) {
-    for (int i = 0; i < steps; ++i) {
-      rc = mpcqp_swarm_step(nominal, relaxed, f, s, stream);
-      if (rc) return rc;
-    }
-    return MPCQP_OK;
-  }
-  return mpcqp::replay_graph(
-      "swarm", user, steps,
-      [&] {
-        const int attrs = set_replan_attrs(s);
-        return attrs != MPCQP_OK ? attrs : mpcqp::fleet_buffers(nominal, relaxed, user);
-      },
-      [&](hipStream_t s2) { return mpcqp_swarm_step(nominal, relaxed, f, s, s2); });
-}
-
-// mpcqp_swarm_step on a changing map, after the swarm's and the map's checks: the fleet step, then the map's
-// trigger and the replanning on each flagged vehicle's grid
-static int swarm_step_map(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s,
-                          const mpcqp_swarm_map* m, void* stream) {
-  int rc = mpcqp_fleet_step(nominal, relaxed, f, stream);
-  if (rc) return rc;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) {
-    rc = set_replan_attrs(s, true);
-    if (rc) return rc;
-  }
-  return enqueue_replan(f, s, st, true, m);
-}
-
-int mpcqp_swarm_run_map(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s,
-                        const mpcqp_swarm_map* m, int steps, int use_graph, void* stream) {
-  int rc = check_swarm(f, s, false);
-  if (rc) return rc;
-  if ((rc = check_map(s, m)) != MPCQP_OK) return rc;
-  if (steps < 0) return fail(MPCQP_E_ARG, "steps must be >= 0");
-  if (!f || f->vehicles == 0 || steps == 0) return mpcqp_fleet_run(nominal, relaxed, f, 0, 0, stream);
-  hipStream_t user = static_cast<hipStream_t>(stream);
-  if (!use_graph) {
-    for (int i = 0; i < steps; ++i) {
-      rc = swarm_step_map(nominal, relaxed, f, s, m, stream);
-      if (rc) return rc;
-    }
-    return MPCQP_OK;
-  }
-  if ((rc = mpcqp_fleet_run(nominal, relaxed, f, 0, 0, stream)) != MPCQP_OK) return rc;  // the fleet's checks
-  return mpcqp::replay_graph(
-      "swarm map", user, steps,
-      [&] {
-        const int attrs = set_replan_attrs(s, true);
-        return attrs != MPCQP_OK ? attrs : mpcqp::fleet_buffers(nominal, relaxed, user);
-      },
-      [&](hipStream_t s2) { return swarm_step_map(nominal, relaxed, f, s, m, s2); });
-}
-
-// mpcqp_swarm_loop on a changing map: the same rounds with k_swarm_loop_map (the blocked test inside the
-// loop) and the replanning on each flagged vehicle's grid; one vehicle per wave, cold, no classes
 int mpcqp_swarm_loop_map(mpcqp_ws* nominal, mpcqp_ws* relaxed, const mpcqp_fleet* f, const mpcqp_swarm* s,
                          const mpcqp_swarm_map* m, void* stream) {
-  int rc = check_swarm(f, s, false);
-  if (rc) return rc;
-  if ((rc = check_map(s, m)) != MPCQP_OK) return rc;
-  rc = mpcqp_fleet_loop(nominal, relaxed, f, 0, stream);  // the fleet's checks (no work at 0 steps)
-  if (rc) return rc;
-  const mpcqp::fleet_loop_t loop = mpcqp::fused_loop(nominal, relaxed, &mpcqp::HorizonKernels::swarm_map);
-  if (f->vehicles == 0) return MPCQP_OK;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (s->max_replans > 0 && (rc = set_replan_attrs(s, true)) != MPCQP_OK) return rc;
-  if (!loop)  // mid / long horizons, reproducible or debug mode: the stepped swarm to the end
-    return mpcqp_swarm_run_map(nominal, relaxed, f, s, m, f->max_steps, 1, stream);
-  mpcqp::LoopLaunch L{nullptr, f, f->max_steps, {s->replan_distance, s->max_replans, s->replans, s->start_goal}};
-  L.map = loop_map(s, m);
-  for (int r = 0; r <= s->max_replans; ++r) {
-    rc = mpcqp::enqueue_fused_loop(nominal, relaxed, loop, "k_swarm_loop_map", MPCQP_LAUNCH_LOOP_MAP, false, L, st);
-    if (rc) return rc;
-    if (r < s->max_replans && (rc = enqueue_replan(f, s, st, false, m)) != MPCQP_OK) return rc;
-  }
-  return MPCQP_OK;
+  return swarm_loop(nominal, relaxed, f, s, m, true, false, 0, stream);
 }
 
 }  // extern "C"

@@ -41,6 +41,19 @@ from .. import _lib
 from ..planning.rrt_star import BatchedRRTStarPlanner, PlannerParameters, pcg64_states
 from .fleet import FleetTracker, relaxed_parameters
 
+# (fused, map, mixed, warm) -> the C call of Swarm.run and what it takes between the swarm struct and the
+# stepped calls' (steps, use_graph).  A combination that is not here is refused before run gets this far
+# (__init__, set_classes, the fleet tracker's check of classes without a table, run's own of classes on a map).
+_CALLS = {
+    (True, False, False, False): ("mpcqp_swarm_loop", ()),
+    (True, False, False, True): ("mpcqp_swarm_loop_warm", ("passes",)),
+    (True, False, True, False): ("mpcqp_swarm_loop_mixed", ("cls",)),
+    (True, False, True, True): ("mpcqp_swarm_loop_mixed_warm", ("cls", "passes")),
+    (True, True, False, False): ("mpcqp_swarm_loop_map", ("map",)),
+    (False, False, False, False): ("mpcqp_swarm_run", ()),
+    (False, True, False, False): ("mpcqp_swarm_run_map", ("map",)),
+}
+
 REPLAN_SEED_STRIDE = 7919  # replan r of vehicle v draws from default_rng(seed_v + 7919 (r + 1))
 
 
@@ -314,26 +327,23 @@ class Swarm:
         t["refs_s"] = time.perf_counter() - t0
         t0 = time.perf_counter()
         stream = torch.cuda.current_stream(self.device)
+        call, names = _CALLS[(bool(self.fused), on_map, mixed, bool(self.warm_start))]
+        given = {"map": lambda: ctypes.byref(mp), "cls": lambda: fb["cls"].data_ptr(),
+                 "passes": lambda: self.guess_passes}
+        args = tuple(given[n]() for n in names)
+
+        def launch(*tail):
+            _lib.check(getattr(self._L, call)(self.fleet._nominal._ws, self.fleet._relaxed._ws,
+                                              ctypes.byref(self.fleet._fleet), ctypes.byref(sw), *args, *tail,
+                                              ctypes.c_void_p(stream.cuda_stream)), call)
+
         done = 0
         if self.fused and V:
-            if on_map:
-                call, args = "mpcqp_swarm_loop_map", (ctypes.byref(mp),)
-            elif mixed:
-                call = "mpcqp_swarm_loop_mixed_warm" if self.warm_start else "mpcqp_swarm_loop_mixed"
-                args = (fb["cls"].data_ptr(),) + ((self.guess_passes,) if self.warm_start else ())
-            else:
-                call, args = (("mpcqp_swarm_loop_warm", (self.guess_passes,)) if self.warm_start
-                              else ("mpcqp_swarm_loop", ()))
-            _lib.check(getattr(self._L, call)(self.fleet._nominal._ws, self.fleet._relaxed._ws,
-                                              ctypes.byref(self.fleet._fleet), ctypes.byref(sw), *args,
-                                              ctypes.c_void_p(stream.cuda_stream)), call)
+            launch()
             done = total
         while done < total and V:
             k = min(check_every, total - done)
-            call, args = ("mpcqp_swarm_run_map", (ctypes.byref(mp),)) if on_map else ("mpcqp_swarm_run", ())
-            _lib.check(getattr(self._L, call)(self.fleet._nominal._ws, self.fleet._relaxed._ws,
-                                              ctypes.byref(self.fleet._fleet), ctypes.byref(sw), *args, int(k),
-                                              int(self.use_graph), ctypes.c_void_p(stream.cuda_stream)), call)
+            launch(int(k), int(self.use_graph))
             done += k
             if not bool((fb["phase"][:V] == _lib.FLEET_RUNNING).any().item()):
                 break
