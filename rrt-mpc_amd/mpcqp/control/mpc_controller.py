@@ -289,28 +289,37 @@ class BatchedMPCController:
         up_t = None if u_prev is None else self._device_input(u_prev, (B, 2), "u_prev")
         if stream is None:
             stream = torch.cuda.current_stream(self.device)
-        s = ctypes.c_void_p(stream.cuda_stream)
         ug_t = None if U_guess is None else self._device_input(U_guess, (B, 2, N), "U_guess")
         self._keep = (x0_t, ref_t, up_t, cls_t, ug_t)  # keep inputs alive until the kernels have consumed them
-        if cls_t is None:
-            _lib.check(self._L.mpcqp_build(self._ws, B, x0_t.data_ptr(), ref_t.data_ptr(),
-                                           None if up_t is None else up_t.data_ptr(), s), "mpcqp_build")
-        else:
-            _lib.check(self._L.mpcqp_build_mixed(self._ws, B, x0_t.data_ptr(), ref_t.data_ptr(),
-                                                 None if up_t is None else up_t.data_ptr(), cls_t.data_ptr(), s),
-                       "mpcqp_build_mixed")
-        if ug_t is not None:
-            passes = _lib.DEFAULT_GUESS_PASSES if guess_passes is None else int(guess_passes)
-            _lib.check(self._L.mpcqp_solve_warm(self._ws, B, ug_t.data_ptr(), passes, self._u0.data_ptr(),
-                                                self._X.data_ptr(), self._U.data_ptr(), self._status.data_ptr(),
-                                                self._iters.data_ptr(), self._active.data_ptr(), s),
-                       "mpcqp_solve_warm")
-        else:
-            _lib.check(self._L.mpcqp_solve(self._ws, B, self._u0.data_ptr(), self._X.data_ptr(), self._U.data_ptr(),
-                                           self._status.data_ptr(), self._iters.data_ptr(), self._active.data_ptr(), s),
-                       "mpcqp_solve")
+        self.solve_raw(B, x0_t, ref_t, up_t, stream, classes=cls_t, U_guess=ug_t, guess_passes=guess_passes)
         return BatchSolution(self._u0[:B], self._X[:B], self._U[:B], self._status[:B], self._iters[:B],
                              self._active[:B])
+
+    def solve_raw(self, B, x0, ref, u_prev, stream, *, classes=None, U_guess=None, guess_passes=None,
+                  after_build=None) -> None:
+        """The two library calls of one batch solve, on tensors as the C-ABI reads them: ``mpcqp_build`` (with
+        ``classes`` ``mpcqp_build_mixed``), then ``mpcqp_solve`` (with ``U_guess`` ``mpcqp_solve_warm``), enqueued
+        on ``stream`` (a torch stream) into the controller's own output tensors (``_u0``, ``_X``, ``_U``,
+        ``_status``, ``_iters``, ``_active``; rows ``[:B]``).  Contiguous device tensors: ``x0`` (B, 4), ``ref``
+        (B, N+1, 4) and ``U_guess`` (B, 2, N) float64, ``u_prev`` (B, 2) float64 or None, ``classes`` (B,) int32.
+        Nothing is converted, checked or kept alive here: ``solve_batch`` does that and then calls this; the
+        measuring tools call it directly.  ``after_build``: called between the two enqueues (an event record)."""
+        s = ctypes.c_void_p(stream.cuda_stream)
+        up = None if u_prev is None else u_prev.data_ptr()
+        if classes is None:
+            _lib.check(self._L.mpcqp_build(self._ws, B, x0.data_ptr(), ref.data_ptr(), up, s), "mpcqp_build")
+        else:
+            _lib.check(self._L.mpcqp_build_mixed(self._ws, B, x0.data_ptr(), ref.data_ptr(), up, classes.data_ptr(), s),
+                       "mpcqp_build_mixed")
+        if after_build is not None:
+            after_build()
+        outs = (self._u0.data_ptr(), self._X.data_ptr(), self._U.data_ptr(), self._status.data_ptr(),
+                self._iters.data_ptr(), self._active.data_ptr())
+        if U_guess is not None:
+            passes = _lib.DEFAULT_GUESS_PASSES if guess_passes is None else int(guess_passes)
+            _lib.check(self._L.mpcqp_solve_warm(self._ws, B, U_guess.data_ptr(), passes, *outs, s), "mpcqp_solve_warm")
+        else:
+            _lib.check(self._L.mpcqp_solve(self._ws, B, *outs, s), "mpcqp_solve")
 
     def solve_one(self, x0, ref, u_prev=None, *, U_guess=None, guess_passes=None):
         """One QP for the sequential closed loop of ``TrajectoryTracker.track``, where host overhead

@@ -194,18 +194,24 @@ class FleetTracker:
         block ``cls[v]`` (class 0 without ``classes``), and ``step`` / ``run`` call
         ``mpcqp_fleet_loop_mixed``.  ``None`` or ``[]`` drops the tables: the tracker is homogeneous
         again.  Needs ``fused=True`` and a horizon of at most 32 (the stepped loop has no classes)."""
+        if params_list:
+            if not self.fused:
+                raise ValueError("set_classes needs fused=True: only the fused loop runs per-vehicle classes")
+            if self.warm_start:
+                raise ValueError("set_classes does not combine with warm_start: the warm loop runs one parameter block")
+            if self.horizon > 32:
+                raise ValueError(f"set_classes needs a horizon <= 32 (the fused loop), got {self.horizon}")
+        self._load_classes(params_list, settings, relaxed_settings)
+
+    def _load_classes(self, params_list, settings=None, relaxed_settings=None) -> None:
+        """Load the class tables on both controllers and record them (``None`` or ``[]``: drop them), unchecked:
+        what ``set_classes`` and ``Swarm.set_classes`` do after their own checks."""
         if not params_list:
             self._nominal.set_classes(None)
             self._relaxed.set_classes(None)
             self.num_classes = 0
             self._class_params = None
             return
-        if not self.fused:
-            raise ValueError("set_classes needs fused=True: only the fused loop runs per-vehicle classes")
-        if self.warm_start:
-            raise ValueError("set_classes does not combine with warm_start: the warm loop runs one parameter block")
-        if self.horizon > 32:
-            raise ValueError(f"set_classes needs a horizon <= 32 (the fused loop), got {self.horizon}")
         params_list = list(params_list)
         self._nominal.set_classes(params_list, settings)
         self._relaxed.set_classes([relaxed_parameters(p) for p in params_list],
@@ -366,7 +372,6 @@ class FleetTracker:
         if stream is None:
             stream = torch.cuda.current_stream(self.device)
         s = ctypes.c_void_p(stream.cuda_stream)
-        fleet = (self._nominal._ws, self._relaxed._ws, ctypes.byref(self._fleet))
         if self.num_classes:  # a class per vehicle (set_classes: fused only)
             call, args = "mpcqp_fleet_loop_mixed", (self._bufs["cls"].data_ptr(), int(steps))
         elif self.carry_guess:  # warm, and the first step of this launch from the last step of the launch before
@@ -377,7 +382,16 @@ class FleetTracker:
             call, args = "mpcqp_fleet_loop", (int(steps),)
         else:
             call, args = "mpcqp_fleet_run", (int(steps), int(self.use_graph))
-        _lib.check(getattr(self._L, call)(*fleet, *args, s), call)
+        _lib.check(getattr(self._L, call)(*self.loop_args(), *args, s), call)
+
+    def loop_args(self) -> tuple:
+        """The three leading arguments of every loop call (``step``'s and ``Swarm.run``'s): the two workspaces and
+        the loaded fleet."""
+        return self._nominal._ws, self._relaxed._ws, ctypes.byref(self._fleet)
+
+    def launch_info(self) -> dict:
+        """What the last loop launch did: the nominal controller's ``launch_info()``."""
+        return self._nominal.launch_info()
 
     def running(self) -> int:
         return int((self._bufs["phase"][: self.vehicles] == _lib.FLEET_RUNNING).sum().item())

@@ -39,7 +39,7 @@ import numpy as np
 
 from .. import _lib
 from ..planning.rrt_star import BatchedRRTStarPlanner, PlannerParameters, pcg64_states
-from .fleet import FleetTracker, relaxed_parameters
+from .fleet import FleetTracker
 
 # (fused, map, mixed, warm) -> the C call of Swarm.run and what it takes between the swarm struct and the
 # stepped calls' (steps, use_graph).  A combination that is not here is refused before run gets this far
@@ -193,31 +193,21 @@ class Swarm:
         tables: the swarm is homogeneous again.  Needs ``fused=True`` and a horizon of at most 32 (the
         stepped swarm has no classes), and one dt: the replanning builds every vehicle's new reference
         with the swarm's ``mpc.dt``, so every class must have it."""
-        fleet = self.fleet
-        if not params_list:
-            fleet._nominal.set_classes(None)
-            fleet._relaxed.set_classes(None)
-            fleet.num_classes = 0
-            fleet._class_params = None
-            return
-        if self.grids is not None:
-            raise ValueError("set_classes on a swarm with grids: the changing map runs one parameter block")
-        if not self.fused:
-            raise ValueError("set_classes needs fused=True: only the fused swarm loop runs per-vehicle classes")
-        if fleet.horizon > 32:
-            raise ValueError(f"set_classes needs a horizon <= 32 (the fused loop), got {fleet.horizon}")
-        params_list = list(params_list)
-        for k, p in enumerate(params_list):
-            if float(p.dt) != float(self.mpc.dt):
-                raise ValueError(f"the swarm runs one dt: class {k} has dt {float(p.dt)}, the swarm's replanning "
-                                 f"builds references with mpc.dt = {float(self.mpc.dt)}")
+        if params_list:
+            if self.grids is not None:
+                raise ValueError("set_classes on a swarm with grids: the changing map runs one parameter block")
+            if not self.fused:
+                raise ValueError("set_classes needs fused=True: only the fused swarm loop runs per-vehicle classes")
+            if self.fleet.horizon > 32:
+                raise ValueError(f"set_classes needs a horizon <= 32 (the fused loop), got {self.fleet.horizon}")
+            params_list = list(params_list)
+            for k, p in enumerate(params_list):
+                if float(p.dt) != float(self.mpc.dt):
+                    raise ValueError(f"the swarm runs one dt: class {k} has dt {float(p.dt)}, the swarm's replanning "
+                                     f"builds references with mpc.dt = {float(self.mpc.dt)}")
         # not through FleetTracker.set_classes: the swarm's tracker is built with fused=False (the swarm
         # issues the fused calls itself) and would refuse
-        fleet._nominal.set_classes(params_list, settings)
-        fleet._relaxed.set_classes([relaxed_parameters(p) for p in params_list],
-                                   settings if relaxed_settings is None else relaxed_settings)
-        fleet.num_classes = len(params_list)
-        fleet._class_params = params_list
+        self.fleet._load_classes(params_list, settings, relaxed_settings)
 
     def _plan(self, starts, goals, seeds):
         """Final paths of every problem (growth, extraction, pruning and smoothing on the device);
@@ -333,8 +323,7 @@ class Swarm:
         args = tuple(given[n]() for n in names)
 
         def launch(*tail):
-            _lib.check(getattr(self._L, call)(self.fleet._nominal._ws, self.fleet._relaxed._ws,
-                                              ctypes.byref(self.fleet._fleet), ctypes.byref(sw), *args, *tail,
+            _lib.check(getattr(self._L, call)(*self.fleet.loop_args(), ctypes.byref(sw), *args, *tail,
                                               ctypes.c_void_p(stream.cuda_stream)), call)
 
         done = 0
@@ -345,10 +334,15 @@ class Swarm:
             k = min(check_every, total - done)
             launch(int(k), int(self.use_graph))
             done += k
-            if not bool((fb["phase"][:V] == _lib.FLEET_RUNNING).any().item()):
+            if not self.fleet.running():
                 break
         torch.cuda.synchronize(self.device)
         t["track_replan_s"] = time.perf_counter() - t0
+        return self._result(V, planned, found, sb, mb, t)
+
+    def _result(self, V: int, planned, found, sb: dict, mb: Optional[dict], t: dict) -> SwarmResult:
+        """The finished run on the host: the fleet's result, and from the swarm's buffers ``sb`` (and the map's
+        ``mb``, None off a map) the replans, their steps, the last replanned paths and the map extras."""
         r = self.fleet.result()
         replans = sb["replans"][:V].cpu().numpy().astype(np.int64)
         replans = np.where(planned, replans, 0)
@@ -365,7 +359,7 @@ class Swarm:
             else:
                 last_paths.append(None)
         extra = {}
-        if on_map:  # causes from the device; the grids of the replans and the hits are host arithmetic on the result
+        if mb is not None:  # causes from the device; the grids of the replans and the hits are host arithmetic on the result
             cause = mb["replan_cause"][:V, : max(self.max_replans, 1)].cpu().numpy()
             extra = dict(replan_cause=np.where(np.arange(cause.shape[1])[None, :] < replans[:, None], cause, 0),
                          replan_grid=replan_grids(replans, rsteps, self.epoch_steps, self.grids.shape[0]),
@@ -374,6 +368,14 @@ class Swarm:
                            paths=found, replan_steps=rsteps, last_replan_start=sg[:, :2].copy(),
                            last_replan_path=last_paths, inputs=r.inputs, timings=t,
                            replan_over_capacity=over_cap, **extra)
+
+    def launch_info(self) -> dict:
+        """What the last fused-loop launch did (``FleetTracker.launch_info``)."""
+        return self.fleet.launch_info()
+
+    def close(self) -> None:
+        """Free the two controllers' workspaces; a second call does nothing."""
+        self.fleet.close()
 
 
 # ------------------------------------------------------------------ multi-GPU: vehicles sharded over ranks

@@ -153,6 +153,19 @@ def fleet5(vehicles: int = 100, seed: int = 5):
     return paths, starts, goals
 
 
+def pairs(occ, V, seed):
+    """V (start, goal) pairs of free cells of ``occ`` more than 30 px apart: the swarm's trips (config 5)."""
+    rng = np.random.default_rng(seed)
+    free = np.argwhere(occ == 1)
+    starts, goals = [], []
+    while len(starts) < V:
+        a, b = free[rng.integers(0, len(free), 2)]
+        if np.hypot(*(a - b)) > 30:  # keep the trips non-trivial
+            starts.append(a[::-1].astype(float))
+            goals.append(b[::-1].astype(float))
+    return np.array(starts), np.array(goals)
+
+
 CONFIGS = {"config2": config2, "config3": config3, "config4": config4}
 
-__all__ = ["Batch", "config2", "config3", "config4", "fleet5", "CONFIGS", "load_default_plan", "window"]
+__all__ = ["Batch", "config2", "config3", "config4", "fleet5", "pairs", "CONFIGS", "load_default_plan", "window"]

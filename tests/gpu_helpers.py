@@ -12,6 +12,7 @@ import numpy as np
 import warm_newton as wn
 from host_helpers import E_ARG, E_HORIZON, E_STATE  # noqa: F401  (the return codes, for the test files)
 from mpcqp._lib import BAD_CLASS  # noqa: F401  (MPCQP_BAD_CLASS; the binding loads the library lazily)
+from mpcqp.scenarios import pairs  # noqa: F401  (the swarm's trips; the swarm test files import it from here)
 from param_variants import VARIANTS, resolution, variant
 
 # ---------------------------------------------------------------------- 1. constants
@@ -211,19 +212,6 @@ def run_loop(ft, paths, starts, goals, steps=None):
     bufs = loop_buffers(ft, LOOP_BUFFERS_MASK)
     ft.close()
     return res, bufs
-
-
-def pairs(occ, V, seed):
-    """V (start, goal) pairs of free cells more than 30 px apart."""
-    rng = np.random.default_rng(seed)
-    free = np.argwhere(occ == 1)
-    starts, goals = [], []
-    while len(starts) < V:
-        a, b = free[rng.integers(0, len(free), 2)]
-        if np.hypot(*(a - b)) > 30:  # keep the trips non-trivial
-            starts.append(a[::-1].astype(float))
-            goals.append(b[::-1].astype(float))
-    return np.array(starts), np.array(goals)
 
 
 def planner_params(seed=13):

@@ -112,6 +112,37 @@ def test_one_class_equals_plain_solve_batch_bitwise(cuda, N):
     assert (plain["status"] == 1).any(), plain["status"]
 
 
+@pytest.mark.parametrize("case", ["cold", "guess", "classes"])
+def test_solve_raw_equals_solve_batch_bitwise(cuda, case):
+    """``solve_raw`` on device tensors in the C layout == ``solve_batch`` on the same tensors, all six outputs:
+    cold, from a guess (the cold U shifted one step), and with classes (two blocks).  The outputs are
+    overwritten between the two, so equal bits are the raw call's own."""
+    import torch
+    from mpcqp import scenarios
+    from mpcqp.control.mpc_controller import BatchSolution
+
+    N, B = 10, 8
+    batch = scenarios.config3(B, horizon=N, seed=4000 + N)
+    ctrl = controller(base_params(N), B)
+    x0, ref, up = (torch.from_numpy(a).to(cuda) for a in (batch.x0, batch.ref, batch.u_prev))
+    kw = {}
+    if case == "guess":
+        U = ctrl.solve_batch(x0, ref, up).U
+        kw = dict(U_guess=torch.cat([U[:, :, 1:], U[:, :, -1:]], dim=2).contiguous())
+    elif case == "classes":
+        ctrl.set_classes(variant_blocks(N, VARIANTS[:2]))
+        kw = dict(classes=torch.from_numpy((np.arange(B) % 2).astype(np.int32)).to(cuda))
+    want = take(ctrl.solve_batch(x0, ref, up, **kw))
+    outs = BatchSolution(ctrl._u0, ctrl._X, ctrl._U, ctrl._status, ctrl._iters, ctrl._active)
+    for t in outs:
+        t.fill_(77)
+    assert ctrl.solve_raw(B, x0, ref, up, torch.cuda.current_stream(cuda), **kw) is None
+    got = take(outs)
+    ctrl.close()
+    assert_same(got, want, f"solve_raw ({case})")
+    assert (want["status"] == 1).any(), want["status"]  # solves, not a batch of early exits
+
+
 # ---------------------------------------------------------------------- 3. settings per class
 def test_classes_differ_in_solver_settings(cuda):
     """Class 0 the defaults, class 1 one ADMM iteration without polish: solved and max_iter side by

@@ -176,6 +176,20 @@ def test_fused_loop_equals_stepped_loop_bitwise(cuda, golden, N, V, steps, seed)
     assert (res.phase != 0).all() or (res.steps == steps).all()
 
 
+def test_fleet_launch_info_is_the_nominal_controllers(cuda, golden):
+    from mpcqp import _lib
+
+    V = 4
+    g, paths, starts, goals = varied_fleet(golden, V, seed=3)
+    ft = fleet_tracker(10, V, 128, 5, fused=True)
+    ft.reset_from_plans(paths, starts, goals)
+    ft.run()
+    info = ft.launch_info()
+    assert info == ft._nominal.launch_info()
+    assert info["kind"] != _lib.LAUNCH_NONE and info["count"] == V, info
+    ft.close()
+
+
 def test_fused_loop_partial_runs_and_resume(cuda, golden):
     """steps < needed: the fused loop stops every vehicle after that many steps and a second call
     resumes from the device state -- the same as stepping."""

@@ -135,6 +135,22 @@ def test_swarm_vehicles_follow_the_reference_loop(cuda, golden):
     assert np.isin(done, [_lib.FLEET_GOAL, _lib.FLEET_OUT_OF_STEPS]).all()
 
 
+def test_swarm_launch_info_and_close(cuda, golden):
+    from mpcqp import _lib
+
+    occ = golden("default_plan.npz")["occupancy"]
+    V = 3
+    starts, goals = pairs(occ, V, 1)
+    sw = swarm(occ, V, 5, fused=True)
+    sw.run(starts, goals, seeds=np.arange(V))
+    info = sw.launch_info()
+    assert info == sw.fleet._nominal.launch_info() and info["kind"] != _lib.LAUNCH_NONE, info
+    sw.close()
+    assert sw.fleet._nominal.closed and sw.fleet._relaxed.closed
+    sw.close()  # harmless
+    assert sw.fleet._nominal.closed and sw.fleet._relaxed.closed
+
+
 def test_per_step_replan_100_vehicles(cuda, golden):
     """BASELINE config 5 at its size: 100 vehicles on the default inflated grid, the trigger
     evaluated on the device after EVERY step.  Every initial plan is the reference planner's; every

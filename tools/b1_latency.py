@@ -31,14 +31,13 @@ own closed loop (its windows, and as the guess of window k the U of window k - 1
 from __future__ import annotations
 
 import argparse
-import ctypes
 import json
 import sys
 import time
 from pathlib import Path
-from types import SimpleNamespace
 
 import numpy as np
+from bench_common import default_track_args, interleaved
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path[:0] = [str(ROOT / "rrt-mpc_amd"), str(ROOT)]
@@ -57,11 +56,8 @@ def best_of(fn, calls: int, reps: int = 5) -> float:
 
 def _median_blocks(fns: dict, reps: int) -> tuple:
     """(name -> median over `reps` of fn() (a time), name -> every repeat), the functions taking turns
-    within each repeat"""
-    got = {name: [] for name in fns}
-    for _ in range(reps):
-        for name, fn in fns.items():
-            got[name].append(fn())
+    within each repeat: always in the order given, and every block warms itself up, so no repeat 0"""
+    got, _ = interleaved(fns, reps, rotate=False, warmup=False)
     return {name: float(np.median(v)) for name, v in got.items()}, got
 
 
@@ -69,21 +65,18 @@ def warm_horizon(N: int, reps: int) -> dict:
     """The cold and the warm B = 1 path at horizon N on the config-1 plan (see the module docstring)."""
     import torch
 
-    from mpcqp import _lib, scenarios
+    from mpcqp import _lib
     from mpcqp.config import MPCConfig, VizConfig
     from mpcqp.control.mpc_controller import _single_controller
     from mpcqp.control.vehicle_model import f_discrete
     from mpcqp.control.ref_builder import build_reference
     from mpcqp.pipeline.control_stage import TrajectoryTracker, window_at
 
-    plan = scenarios.load_default_plan()
-    path = [tuple(map(float, q)) for q in plan["path"]]
-    planning = SimpleNamespace(plan=SimpleNamespace(success=True, path=path))
-    maps = SimpleNamespace(start=tuple(plan["start"]), goal=tuple(plan["goal"]))
+    planning, maps = default_track_args()
+    path = planning.plan.path
     mpc = MPCConfig(horizon=N, sim_steps=300)
     params = mpc.to_parameters(0.8)
     ctrl = _single_controller(params)
-    L = _lib.lib()
 
     # the loop's own windows and optima (TrajectoryTracker.track's loop, cold)
     state = np.array([maps.start[0], maps.start[1], np.arctan2(path[1][1] - path[0][1], path[1][0] - path[0][0]), 5.0])
@@ -142,21 +135,13 @@ def warm_horizon(N: int, reps: int) -> dict:
     x0_t, w_t, up_t = (torch.from_numpy(np.stack(v)).to(dev) for v in (x0s, wins, ups))
     g_t = torch.from_numpy(np.stack([Us[0]] + guesses[1:])).to(dev)
     stream = torch.cuda.current_stream(dev)
-    s = ctypes.c_void_p(stream.cuda_stream)
-    outs = [t.data_ptr() for t in (ctrl._u0, ctrl._X, ctrl._U, ctrl._status, ctrl._iters, ctrl._active)]
 
     def kernel(warm):
         def block():
             ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
             for q in range(1, n):
                 ev[q][0].record(stream)
-                _lib.check(L.mpcqp_build(ctrl._ws, 1, x0_t[q].data_ptr(), w_t[q].data_ptr(), up_t[q].data_ptr(), s),
-                           "build")
-                if warm:
-                    _lib.check(L.mpcqp_solve_warm(ctrl._ws, 1, g_t[q].data_ptr(), _lib.DEFAULT_GUESS_PASSES, *outs, s),
-                               "solve_warm")
-                else:
-                    _lib.check(L.mpcqp_solve(ctrl._ws, 1, *outs, s), "solve")
+                ctrl.solve_raw(1, x0_t[q], w_t[q], up_t[q], stream, U_guess=g_t[q] if warm else None)
                 ev[q][1].record(stream)
                 torch.cuda.synchronize(dev)
             return float(np.mean([e0.elapsed_time(e1) * 1e3 for e0, e1 in ev[1:]]))
@@ -198,7 +183,7 @@ def main() -> None:
         return
     import torch
 
-    from mpcqp import _lib, scenarios
+    from mpcqp import _lib
     from mpcqp.config import MPCConfig, VizConfig
     from mpcqp.control.mpc_controller import MPCController, _single_controller
     from mpcqp.pipeline.control_stage import TrajectoryTracker
@@ -238,32 +223,24 @@ def main() -> None:
     w_t = torch.from_numpy(wins).to(dev)
     up_t = torch.from_numpy(ups).to(dev)
     stream = torch.cuda.current_stream(dev)
-    s = ctypes.c_void_p(stream.cuda_stream)
 
     def device_call(k):
         q = k % n
-        _lib.check(L.mpcqp_build(ctrl._ws, 1, x0_t[q].data_ptr(), w_t[q].data_ptr(), up_t[q].data_ptr(), s), "build")
-        _lib.check(L.mpcqp_solve(ctrl._ws, 1, ctrl._u0.data_ptr(), ctrl._X.data_ptr(), ctrl._U.data_ptr(),
-                                 ctrl._status.data_ptr(), ctrl._iters.data_ptr(), ctrl._active.data_ptr(), s), "solve")
+        ctrl.solve_raw(1, x0_t[q], w_t[q], up_t[q], stream)
         torch.cuda.synchronize(dev)
 
     out["device_inputs_us"] = best_of(device_call, a.calls)
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
     for q in range(n):
         ev[q][0].record(stream)
-        _lib.check(L.mpcqp_build(ctrl._ws, 1, x0_t[q].data_ptr(), w_t[q].data_ptr(), up_t[q].data_ptr(), s), "build")
-        _lib.check(L.mpcqp_solve(ctrl._ws, 1, ctrl._u0.data_ptr(), ctrl._X.data_ptr(), ctrl._U.data_ptr(),
-                                 ctrl._status.data_ptr(), ctrl._iters.data_ptr(), ctrl._active.data_ptr(), s), "solve")
+        ctrl.solve_raw(1, x0_t[q], w_t[q], up_t[q], stream)
         ev[q][1].record(stream)
         torch.cuda.synchronize(dev)
     ks = np.array([e0.elapsed_time(e1) * 1e3 for e0, e1 in ev])
     out["kernel_event_us"] = {"mean": float(ks.mean()), "min": float(ks.min()), "max": float(ks.max())}
 
-    plan = scenarios.load_default_plan()
-    path = [tuple(map(float, q)) for q in plan["path"]]
     tracker = TrajectoryTracker(MPCConfig(horizon=N, sim_steps=100), VizConfig())
-    planning = SimpleNamespace(plan=SimpleNamespace(success=True, path=path))
-    maps = SimpleNamespace(start=tuple(plan["start"]), goal=tuple(plan["goal"]))
+    planning, maps = default_track_args()
     tracker.track(planning, maps, map_resolution=0.8, visualize=False)
     best = None
     for _ in range(5):

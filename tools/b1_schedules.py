@@ -8,14 +8,13 @@ optimum; the states must agree with the reference loop (closed_loop.npz) to 1e-7
 """
 from __future__ import annotations
 
-import ctypes
 import json
 import sys
 import time
 from pathlib import Path
-from types import SimpleNamespace
 
 import numpy as np
+from bench_common import default_track_args
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path[:0] = [str(ROOT / "rrt-mpc_amd"), str(ROOT)]
@@ -32,7 +31,6 @@ SCHEDULES = [
 def main() -> None:
     import torch
 
-    from mpcqp import _lib, scenarios
     from mpcqp.config import MPCConfig, VizConfig
     from mpcqp.control.mpc_controller import BatchedMPCController
     from mpcqp.pipeline.control_stage import TrajectoryTracker
@@ -40,14 +38,10 @@ def main() -> None:
     g = np.load(ROOT / "tests" / "golden" / "closed_loop.npz")
     ref_states = g["N10_states"]
     wins, x0s, ups = g["N10_window"], g["N10_x0"], g["N10_u_prev"]
-    plan = scenarios.load_default_plan()
-    path = [tuple(map(float, q)) for q in plan["path"]]
-    planning = SimpleNamespace(plan=SimpleNamespace(success=True, path=path))
-    maps = SimpleNamespace(start=tuple(plan["start"]), goal=tuple(plan["goal"]))
+    planning, maps = default_track_args()
     params = MPCConfig(horizon=10).to_parameters(0.8)
     dev = torch.device("cuda:0")
     x0_t, w_t, up_t = (torch.from_numpy(a).to(dev) for a in (x0s, wins, ups))
-    L = _lib.lib()
     out = []
     for sched in SCHEDULES:
         tr = TrajectoryTracker(MPCConfig(horizon=10, sim_steps=100), VizConfig(), solver_settings=dict(sched),
@@ -62,15 +56,12 @@ def main() -> None:
         dev_px = float(np.abs(np.asarray(st) - ref_states).max()) if len(st) == len(ref_states) else None
         ctrl = BatchedMPCController(params, 1, device=dev, **sched)
         stream = torch.cuda.current_stream(dev)
-        s = ctypes.c_void_p(stream.cuda_stream)
         ks, its = [], []
         for rep in range(2):
             for q in range(len(wins)):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record(stream)
-                _lib.check(L.mpcqp_build(ctrl._ws, 1, x0_t[q].data_ptr(), w_t[q].data_ptr(), up_t[q].data_ptr(), s), "b")
-                _lib.check(L.mpcqp_solve(ctrl._ws, 1, ctrl._u0.data_ptr(), ctrl._X.data_ptr(), ctrl._U.data_ptr(),
-                                         ctrl._status.data_ptr(), ctrl._iters.data_ptr(), ctrl._active.data_ptr(), s), "s")
+                ctrl.solve_raw(1, x0_t[q], w_t[q], up_t[q], stream)
                 e1.record(stream)
                 torch.cuda.synchronize(dev)
                 if rep:

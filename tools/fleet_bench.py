@@ -28,31 +28,30 @@ import json
 import sys
 import time
 from pathlib import Path
-from types import SimpleNamespace
 
 import numpy as np
+from bench_common import class_blocks, interleaved, loop_counts, summary, timed, track_args
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT / "rrt-mpc_amd"))
 
 
-def class_blocks(base, K):
-    """K parameter blocks of one horizon and dt: the base, then other wheelbases, limits and weights."""
-    from dataclasses import replace
+def seconds(ts) -> dict:
+    """``bench_common.summary`` under this tool's key names."""
+    s = summary(ts)
+    return {"seconds_median": s["median"], "seconds_min": s["min"], "seconds_max": s["max"], "seconds": s["all"]}
 
-    pool = [
-        base,
-        replace(base, wheelbase_px=base.wheelbase_px * 4.0),  # the wheelbase at map_resolution 0.2
-        replace(base, u_bounds=((-5.0, 4.0), (-0.3, 0.25)), v_bounds=(2.0, 18.0), du_bounds=((-3.0, 2.5), (-0.05, 0.04))),
-        replace(base, q=np.array(base.q) * 2.0, q_terminal=np.array(base.q_terminal) * 2.0),
-        replace(base, r=np.array(base.r) * 4.0),
-        replace(base, v_bounds=(0.0, 12.0)),
-        replace(base, wheelbase_px=base.wheelbase_px * 2.0, du_bounds=((-8.0, 8.0), (-0.1, 0.1))),
-        replace(base, slack_velocity=1e4, slack_input=5e3, slack_rate=5e3),
-    ]
-    if not 1 <= K <= len(pool):
-        raise SystemExit(f"--classes takes 1..{len(pool)}")
-    return pool[:K]
+
+def loop_leg(fts, steps: int, K: int):
+    """A leg of ``interleaved``: the seconds of ``steps`` steps of each tracker of ``fts`` in turn, as launches of
+    K steps, up to a synchronise."""
+    import torch
+
+    def launches():
+        for ft in fts:
+            for _ in range(-(-steps // K)):
+                ft.step(K)
+    return lambda: timed(launches, torch.cuda.synchronize, time.perf_counter)[0]
 
 
 def mixed_bench(a) -> None:
@@ -89,35 +88,20 @@ def mixed_bench(a) -> None:
             for ft, g in zip(subs, groups):
                 ft.reset_from_plans([paths[i] for i in g], starts[g], goals[g], device_reference=True)
 
-        def timed(fts):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for ft in fts:
-                ft.step(a.steps)
-            torch.cuda.synchronize()
-            return time.perf_counter() - t0
-
-        names = ["split", *mixes]
-        times = {k: [] for k in [*mixes, "split"]}
-        for r in range(2 * a.reps + 1):  # repeat 0 warms up; then the order rotates
-            load()
-            for side in names[r % len(names):] + names[:r % len(names)]:
-                dt = timed([mixes[side]] if side in mixes else subs)
-                if r:
-                    times[side].append(dt)
+        # 2 reps + 1 repeats, the fleets loaded again before each
+        times, _ = interleaved({"split": loop_leg(subs, a.steps, a.steps),
+                                **{side: loop_leg([ft], a.steps, a.steps) for side, ft in mixes.items()}}, 2 * a.reps, load)
         rm = mixed.result()
         steps_split = np.zeros(V, dtype=np.int64)
         for ft, g in zip(subs, groups):
             steps_split[g] = ft.result().steps
         vsteps = int(rm.steps.sum())
-        run = {"vehicles": V, "vehicle_steps": vsteps, "same_step_counts": bool((steps_split == rm.steps).all()),
-               "goal_reached": int((rm.phase == 1).sum()), "aborted": int((rm.phase == 2).sum()),
+        run = {"vehicles": V, **loop_counts(rm), "same_step_counts": bool((steps_split == rm.steps).all()),
                "max_steps_of_a_vehicle": int(rm.steps.max())}
-        for side, ts in times.items():
-            run[side] = {"seconds_median": float(np.median(ts)), "seconds_min": min(ts), "seconds_max": max(ts),
-                         "seconds": ts, "value": vsteps / float(np.median(ts))}
+        for side in [*mixes, "split"]:
+            run[side] = {**seconds(times[side]), "value": vsteps / float(np.median(times[side]))}
         for side, ft in mixes.items():
-            info, rs = ft._nominal.launch_info(), ft.result()
+            info, rs = ft.launch_info(), ft.result()
             run[side].update(per_wave=info["per_wave"], workgroups=info["workgroups"],
                              same_steps_and_phases=bool((rs.steps == rm.steps).all() and (rs.phase == rm.phase).all()))
             run[f"{side}_over_split_time"] = run[side]["seconds_median"] / run["split"]["seconds_median"]
@@ -181,28 +165,20 @@ def warm_bench(a) -> None:
                     chunk[k] = K
         names = list(sides)
         first_cold = names[0]
-        times = {k: [] for k in names}
-        for r in range(a.reps + 1):  # repeat 0 warms up
+
+        def load():
             for ft in sides.values():
                 ft.reset_from_plans(paths, starts, goals, device_reference=a.plan != "config1")
-            for k in names[r % len(names):] + names[:r % len(names)]:
-                K = chunk.get(k, a.steps)
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                for _ in range(-(-a.steps // K)):
-                    sides[k].step(K)
-                torch.cuda.synchronize()
-                if r:
-                    times[k].append(time.perf_counter() - t0)
+
+        times, _ = interleaved({k: loop_leg([ft], a.steps, chunk.get(k, a.steps)) for k, ft in sides.items()}, a.reps, load)
         res = {k: ft.result() for k, ft in sides.items()}
-        launches = {k: sides[k]._nominal.launch_info() for k in names}
+        launches = {k: sides[k].launch_info() for k in names}
         cold = res[first_cold]
-        run = {"vehicles": V, "vehicle_steps": int(cold.steps.sum()), "goal_reached": int((cold.phase == 1).sum()),
-               "aborted": int((cold.phase == 2).sum())}
+        run = {"vehicles": V, **loop_counts(cold)}
         for k in names:
             ts, rk = times[k], res[k]
             med = float(np.median(ts))
-            run[k] = {"seconds_median": med, "seconds_min": min(ts), "seconds_max": max(ts), "seconds": ts,
+            run[k] = {**seconds(ts),
                       "value": int(rk.steps.sum()) / med, "time_over_cold": med / float(np.median(times[first_cold])),
                       "launches": -(-a.steps // chunk.get(k, a.steps)), "per_wave": launches[k]["per_wave"],
                       "workgroups": launches[k]["workgroups"],
@@ -289,9 +265,7 @@ def main() -> None:
         dt, res, loop_dt, reset_dt = best
         vsteps = int(res.steps.sum())
         out["runs"].append({
-            "vehicles": V, "seconds": dt, "vehicle_steps": vsteps, "value": vsteps / dt,
-            "goal_reached": int((res.phase == 1).sum()), "aborted": int((res.phase == 2).sum()),
-            "ms_per_step": 1e3 * dt / a.steps,
+            "vehicles": V, "seconds": dt, **loop_counts(res), "value": vsteps / dt, "ms_per_step": 1e3 * dt / a.steps,
             # the loop alone (ft.step after the references are built and loaded): the fused kernel
             "loop_seconds": loop_dt, "loop_value": vsteps / loop_dt, "reset_seconds": reset_dt,
         })
@@ -300,8 +274,7 @@ def main() -> None:
     # reference-style host loop: one vehicle, one solve (B=1 kernel launch + sync) per step
     paths, starts, goals = scenarios.fleet5(1)
     tr = TrajectoryTracker(MPCConfig(horizon=a.horizon, sim_steps=a.steps), VizConfig())
-    planning = SimpleNamespace(plan=SimpleNamespace(success=True, path=[tuple(map(float, q)) for q in paths[0]]))
-    maps = SimpleNamespace(start=tuple(starts[0]), goal=tuple(goals[0]))
+    planning, maps = track_args(paths[0], starts[0], goals[0])
     tr.track(planning, maps, map_resolution=0.8, visualize=False)
     t0 = time.perf_counter()
     st = tr.track(planning, maps, map_resolution=0.8, visualize=False).states

@@ -127,6 +127,7 @@ def main() -> None:
     ap.add_argument("--out", type=Path, default=ROOT / "profiles" / "mixed_classes" / "bench.json")
     a = ap.parse_args()
     import torch
+    from bench_common import interleaved
     from param_variants import VARIANTS, resolution, variant
 
     from mpcqp import _lib, scenarios
@@ -167,10 +168,9 @@ def main() -> None:
                                                pairing=_lib.PAIRING_MODES["on"]) for c, p in enumerate(blocks)]
     order = [k for k in ("plain", "plain_parent", "mixed_k1", mixed_k, mixed_k + "_paired", k_plain,
                          k_plain + "_paired") if k in legs]
-    ms = {k: [] for k in order}
-    for _ in range(a.repeats):  # the legs alternate: every repeat visits each once, in this order
-        for k in order:
-            ms[k].append(time_leg(legs[k], a.steps, a.warmup, stream))
+    # the legs alternate: every repeat visits each once, in this order (each timing warms itself up: no repeat 0)
+    ms, _ = interleaved({k: lambda k=k: time_leg(legs[k], a.steps, a.warmup, stream) for k in order}, a.repeats,
+                        rotate=False, warmup=False)
     torch.cuda.synchronize()
     # what the timed launches computed: the same QPs solved, and the same results where they must be
     solved = {k: int(sum(int((w.status == 1).sum()) for w in legs[k])) for k in order}

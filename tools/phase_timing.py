@@ -9,7 +9,6 @@ KKT factorizations, ADMM iterations and polish iterations.
 from __future__ import annotations
 
 import argparse
-import ctypes
 import json
 import sys
 from pathlib import Path
@@ -28,7 +27,7 @@ def main() -> None:
     args = ap.parse_args()
     import torch
 
-    from mpcqp import _lib, scenarios
+    from mpcqp import scenarios
     from mpcqp.config import MPCConfig
     from mpcqp.control.mpc_controller import BatchedMPCController
 
@@ -53,17 +52,12 @@ def main() -> None:
         kw = dict(kw)
         method = kw.pop("method", "admm")
         ctrl = BatchedMPCController(params, args.batch, device=dev, method=method, **kw)
-        L = _lib.lib()
-        s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        stream = torch.cuda.current_stream()
         times = []
         for r in range(args.reps + 1):
             e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
             e0.record()
-            _lib.check(L.mpcqp_build(ctrl._ws, args.batch, x0.data_ptr(), ref.data_ptr(), up.data_ptr(), s), "b")
-            e1.record()
-            _lib.check(L.mpcqp_solve(ctrl._ws, args.batch, ctrl._u0.data_ptr(), ctrl._X.data_ptr(),
-                                     ctrl._U.data_ptr(), ctrl._status.data_ptr(), ctrl._iters.data_ptr(),
-                                     ctrl._active.data_ptr(), s), "s")
+            ctrl.solve_raw(args.batch, x0, ref, up, stream, after_build=e1.record)  # e1: between build and solve
             e2.record()
             torch.cuda.synchronize()
             if r:

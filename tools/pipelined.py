@@ -9,7 +9,6 @@ beside the bench line, not as it: each step is still one whole batch, but S batc
 from __future__ import annotations
 
 import argparse
-import ctypes
 import json
 import sys
 import time
@@ -31,7 +30,6 @@ def main() -> None:
     import torch
 
     import bench
-    from mpcqp import _lib
     from mpcqp.config import MPCConfig
     from mpcqp.control.mpc_controller import BatchedMPCController
 
@@ -39,7 +37,6 @@ def main() -> None:
     dev = torch.device("cuda:0")
     params = MPCConfig(horizon=b.horizon).to_parameters(0.8)
     x0_t, ref_t, up_t = (torch.from_numpy(v).to(dev) for v in (b.x0, b.ref, b.u_prev))
-    L = _lib.lib()
     out = []
     for S in a.streams:
         ctrls = [BatchedMPCController(params, a.batch, device=dev) for _ in range(S)]
@@ -47,11 +44,7 @@ def main() -> None:
         B = a.batch
 
         def step(k):
-            c, st = ctrls[k % S], streams[k % S]
-            s = ctypes.c_void_p(st.cuda_stream)
-            _lib.check(L.mpcqp_build(c._ws, B, x0_t.data_ptr(), ref_t.data_ptr(), up_t.data_ptr(), s), "build")
-            _lib.check(L.mpcqp_solve(c._ws, B, c._u0.data_ptr(), c._X.data_ptr(), c._U.data_ptr(), c._status.data_ptr(),
-                                     c._iters.data_ptr(), c._active.data_ptr(), s), "solve")
+            ctrls[k % S].solve_raw(B, x0_t, ref_t, up_t, streams[k % S])
 
         for k in range(3 * S):
             step(k)

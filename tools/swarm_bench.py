@@ -40,22 +40,63 @@ import time
 from pathlib import Path
 
 import numpy as np
+from bench_common import class_blocks, default_grid, interleaved, loop_counts, summary, timed
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT / "rrt-mpc_amd"))
 sys.path.insert(0, str(ROOT / "oracle"))
 
+from mpcqp.scenarios import pairs  # noqa: E402
 
-def pairs(occ, V, seed):
-    rng = np.random.default_rng(seed)
-    free = np.argwhere(occ == 1)
-    s, g = [], []
-    while len(s) < V:
-        a, b = free[rng.integers(0, len(free), 2)]
-        if np.hypot(*(a - b)) > 30:
-            s.append(a[::-1].astype(float))
-            g.append(b[::-1].astype(float))
-    return np.array(s), np.array(g)
+SWARM_COUNTS = ("vehicle_steps", "goal_reached", "replans")
+
+
+def run_legs(legs: dict, reps: int) -> tuple:
+    """Whole ``Swarm.run`` rounds, interleaved (``bench_common.interleaved``): ``legs[k]()`` runs leg k's swarms
+    and returns their results as a list.  Returns (leg -> the last round's results, leg -> the timed repeats'
+    ``track_replan_s``, summed over the leg's swarms, and ``end_to_end_s``, the window around the round)."""
+    import torch
+
+    def leg(fn):
+        def window():
+            dt, parts = timed(fn, torch.cuda.synchronize, time.perf_counter)
+            return {"track_replan_s": sum(p.timings["track_replan_s"] for p in parts), "end_to_end_s": dt}, parts
+        return window
+
+    values, last = interleaved({k: leg(fn) for k, fn in legs.items()}, reps, value=lambda ret: ret[0])
+    times = {k: {what: [v[what] for v in vs] for what in ("track_replan_s", "end_to_end_s")} for k, vs in values.items()}
+    return {k: ret[1] for k, ret in last.items()}, times
+
+
+def run_swarms(swarms: dict, starts, goals, reps: int) -> tuple:
+    """``run_legs`` where every leg is one swarm on all the vehicles: (leg -> its last result, the times)."""
+    V = len(starts)
+    res, times = run_legs({k: lambda sw=sw: [sw.run(starts, goals, seeds=np.arange(V))] for k, sw in swarms.items()}, reps)
+    return {k: parts[0] for k, parts in res.items()}, times
+
+
+def new_swarm(a, V, device="cuda:0", **kw):
+    """A swarm of up to V vehicles as every mode builds it: the default grid and planner, horizon 15, --steps,
+    --replan-distance and --max-replans; ``kw`` goes to ``Swarm``."""
+    from mpcqp.config import MPCConfig
+    from mpcqp.pipeline.swarm import Swarm
+    from mpcqp.planning.rrt_star import default_planner_parameters
+
+    return Swarm(default_grid(), MPCConfig(horizon=15, sim_steps=a.steps), default_planner_parameters(), map_resolution=0.8,
+                 max_vehicles=V, device=device, replan_distance=a.replan_distance, max_replans=a.max_replans, **kw)
+
+
+def leg_report(sw, rk, ts: dict, base: dict = None, over: str = "") -> dict:
+    """What every interleaved leg reports of its swarm ``sw``, its last result ``rk`` and its times ``ts``: the
+    counts, the launch, and per time its summary, with the ratio of medians to ``base``'s under the key ``over``."""
+    info = sw.launch_info()
+    d = {**loop_counts(rk, SWARM_COUNTS), "vehicles_replanned": int((rk.replans > 0).sum()), "launch": info["name"],
+         "per_wave": info["per_wave"]}
+    for what, t in ts.items():
+        d[what] = summary(t)
+        if base is not None:
+            d[what][over] = d[what]["median"] / float(np.median(base[what]))
+    return d
 
 
 def distributed(a) -> None:
@@ -64,24 +105,17 @@ def distributed(a) -> None:
     import torch
     import torch.distributed as dist
 
-    from mpcqp.config import MPCConfig
-    from mpcqp.pipeline.swarm import Swarm, run_swarm_sharded, shard_vehicles
-    from mpcqp.planning.rrt_star import default_planner_parameters
+    from mpcqp.pipeline.swarm import run_swarm_sharded, shard_vehicles
 
     rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
     local = int(os.environ.get("LOCAL_RANK", rank))
     dev = torch.device("cuda", local % torch.cuda.device_count())
     torch.cuda.set_device(dev)
     dist.init_process_group(a.backend, rank=rank, world_size=world)
-    d = np.load(ROOT / "rrt-mpc_amd" / "mpcqp" / "data" / "default_plan.npz")
-    occ = d["occupancy"]
-    prm = default_planner_parameters()
-    mpc = MPCConfig(horizon=15, sim_steps=a.steps)
     for V in a.vehicles:
-        starts, goals = pairs(occ, V, 5)
+        starts, goals = pairs(default_grid(), V, 5)
         lo, hi = shard_vehicles(V, world, rank)
-        sw = Swarm(occ, mpc, prm, map_resolution=0.8, max_vehicles=max(hi - lo, 1), device=dev,
-                   replan_distance=a.replan_distance, max_replans=a.max_replans, fused=a.fused)
+        sw = new_swarm(a, max(hi - lo, 1), dev, fused=a.fused)
         sw.run(starts[:1], goals[:1], seeds=np.arange(1), sim_steps=5)  # warm
         torch.cuda.synchronize(dev)
         dist.barrier()
@@ -94,9 +128,7 @@ def distributed(a) -> None:
         t = torch.tensor([dt], dtype=torch.float64, device=dev if a.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         if rank == 0:
-            one = Swarm(occ, mpc, prm, map_resolution=0.8, max_vehicles=V, device=dev,
-                        replan_distance=a.replan_distance, max_replans=a.max_replans)
-            ref = one.run(starts, goals, seeds=np.arange(V), check_every=50)
+            ref = new_swarm(a, V, dev).run(starts, goals, seeds=np.arange(V), check_every=50)
             same = (np.array_equal(res.steps, ref.steps) and np.array_equal(res.phase, ref.phase)
                     and np.array_equal(res.replans, ref.replans)
                     and all(np.array_equal(x, y) for x, y in zip(res.states, ref.states)))
@@ -119,57 +151,27 @@ def warm_bench(a) -> None:
     repeat 0 warms up.  Per leg: medians with min and max of track_replan_s (the fused-loop launches and the
     replanning between them, up to a synchronise) and of the end-to-end run (planning and references
     included), vehicle-steps, replans, and whether steps, phases and replan steps agree with the cold leg."""
-    import torch
-
-    from mpcqp.config import MPCConfig
-    from mpcqp.pipeline.swarm import Swarm
-    from mpcqp.planning.rrt_star import default_planner_parameters
-
-    occ = np.load(ROOT / "rrt-mpc_amd" / "mpcqp" / "data" / "default_plan.npz")["occupancy"]
-    prm = default_planner_parameters()
     out = {"metric": "Swarm.run seconds, cold and warm legs interleaved", "horizon": 15, "sim_steps": a.steps,
            "replan_distance": a.replan_distance, "max_replans": a.max_replans, "pairing": a.pairing, "reps": a.reps,
            "runs": []}
     for V in a.vehicles:
-        starts, goals = pairs(occ, V, 5)
-        kw = dict(map_resolution=0.8, max_vehicles=V, device="cuda:0", replan_distance=a.replan_distance,
-                  max_replans=a.max_replans, fused=True, pairing=a.pairing)
-        mpc = MPCConfig(horizon=15, sim_steps=a.steps)
-        legs = {"cold": Swarm(occ, mpc, prm, **kw)}
+        starts, goals = pairs(default_grid(), V, 5)
+        legs = {"cold": new_swarm(a, V, fused=True, pairing=a.pairing)}
         for gp in a.guess_passes:
-            legs[f"warm:{gp}"] = Swarm(occ, mpc, prm, warm_start=True, guess_passes=gp, **kw)
-        names = list(legs)
-        times = {k: {"track_replan_s": [], "end_to_end_s": []} for k in names}
-        res = {}
-        for r in range(a.reps + 1):  # repeat 0 warms up
-            for k in names[r % len(names):] + names[:r % len(names)]:
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                res[k] = legs[k].run(starts, goals, seeds=np.arange(V))
-                torch.cuda.synchronize()
-                if r:
-                    times[k]["end_to_end_s"].append(time.perf_counter() - t0)
-                    times[k]["track_replan_s"].append(res[k].timings["track_replan_s"])
+            legs[f"warm:{gp}"] = new_swarm(a, V, fused=True, pairing=a.pairing, warm_start=True, guess_passes=gp)
+        res, times = run_swarms(legs, starts, goals, a.reps)
         cold = res["cold"]
         run = {"vehicles": V, "planned": int(cold.planned.sum())}
-        for k in names:
-            rk = res[k]
-            info = legs[k].fleet._nominal.launch_info()
-            run[k] = {"vehicle_steps": int(rk.steps.sum()), "goal_reached": int((rk.phase == 1).sum()),
-                      "replans": int(rk.replans.sum()), "replans_with_new_plan": int((rk.replan_steps > 0).sum()),
-                      "vehicles_replanned": int((rk.replans > 0).sum()), "launch": info["name"],
-                      "per_wave": info["per_wave"],
+        for k, rk in res.items():
+            run[k] = {**leg_report(legs[k], rk, times[k], times["cold"], "over_cold"),
+                      "replans_with_new_plan": int((rk.replan_steps > 0).sum()),
                       "same_steps": bool(np.array_equal(rk.steps, cold.steps)),
                       "same_phases": bool(np.array_equal(rk.phase, cold.phase)),
                       "same_replan_steps": bool(np.array_equal(rk.replan_steps, cold.replan_steps)),
                       "vehicles_with_other_steps": int((rk.steps != cold.steps).sum())}
-            for what, ts in times[k].items():
-                med = float(np.median(ts))
-                run[k][what] = {"median": med, "min": min(ts), "max": max(ts), "all": ts,
-                                "over_cold": med / float(np.median(times["cold"][what]))}
         out["runs"].append(run)
         for sw in legs.values():
-            sw.fleet.close()
+            sw.close()
         print(json.dumps(run), flush=True)
     print(json.dumps(out))
 
@@ -181,70 +183,43 @@ def classes_bench(a) -> None:
     the order rotating from repeat to repeat; repeat 0 warms up.  Per leg: medians with min and max of
     track_replan_s (summed over the sub-swarms on the split legs) and of the end-to-end time, vehicle-steps and
     replans, and whether every vehicle's steps, phase and replan steps equal the mixed leg's."""
-    import torch
-    from fleet_bench import class_blocks
-
     from mpcqp.config import MPCConfig
-    from mpcqp.pipeline.swarm import Swarm, merge_swarm_results
-    from mpcqp.planning.rrt_star import default_planner_parameters
+    from mpcqp.pipeline.swarm import merge_swarm_results
 
-    occ = np.load(ROOT / "rrt-mpc_amd" / "mpcqp" / "data" / "default_plan.npz")["occupancy"]
-    prm = default_planner_parameters()
     K = a.classes
     gp = a.guess_passes[0]
     out = {"metric": "Swarm.run seconds: one mixed swarm against its K homogeneous sub-swarms back to back, "
                      "legs interleaved", "horizon": 15, "sim_steps": a.steps, "classes": K,
            "replan_distance": a.replan_distance, "max_replans": a.max_replans, "guess_passes": gp, "reps": a.reps,
            "runs": []}
-    mpc = MPCConfig(horizon=15, sim_steps=a.steps)
-    blocks = class_blocks(mpc.to_parameters(0.8), K)
+    blocks = class_blocks(MPCConfig(horizon=15, sim_steps=a.steps).to_parameters(0.8), K)
     for V in a.vehicles:
-        starts, goals = pairs(occ, V, 5)
+        starts, goals = pairs(default_grid(), V, 5)
         cls = np.arange(V) % K
         idx = [np.flatnonzero(cls == c) for c in range(K)]
         order = np.concatenate(idx)
-        kw = dict(map_resolution=0.8, device="cuda:0", replan_distance=a.replan_distance, max_replans=a.max_replans,
-                  fused=True)
         legs = {}
         for temp, wkw in (("cold", {}), ("warm", dict(warm_start=True, guess_passes=gp))):
-            mixed = Swarm(occ, mpc, prm, max_vehicles=V, **kw, **wkw)
+            mixed = new_swarm(a, V, fused=True, **wkw)
             mixed.set_classes(blocks)
             legs[f"mixed:{temp}"] = [(mixed, np.arange(V), dict(classes=cls))]
-            legs[f"split:{temp}"] = [(Swarm(occ, mpc, prm, max_vehicles=max(len(i), 1), params=blocks[c], **kw, **wkw),
-                                      i, {}) for c, i in enumerate(idx) if len(i)]
-        names = list(legs)
-        times = {k: {"track_replan_s": [], "end_to_end_s": []} for k in names}
-        res = {}
-        for r in range(a.reps + 1):  # repeat 0 warms up
-            for k in names[r % len(names):] + names[:r % len(names)]:
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                parts = [sw.run(starts[i], goals[i], seeds=i, **more) for sw, i, more in legs[k]]
-                torch.cuda.synchronize()
-                if r:
-                    times[k]["end_to_end_s"].append(time.perf_counter() - t0)
-                    times[k]["track_replan_s"].append(sum(p.timings["track_replan_s"] for p in parts))
-                res[k] = parts
+            legs[f"split:{temp}"] = [(new_swarm(a, max(len(i), 1), fused=True, params=blocks[c], **wkw), i, {})
+                                     for c, i in enumerate(idx) if len(i)]
+        res, times = run_legs({k: lambda leg=leg: [sw.run(starts[i], goals[i], seeds=i, **more) for sw, i, more in leg]
+                               for k, leg in legs.items()}, a.reps)
         run = {"vehicles": V, "classes": K}
-        for k in names:
+        for k in legs:
             rk = merge_swarm_results(res[k])  # the split legs: class by class, i.e. in `order`
             sel = np.arange(V) if k.startswith("mixed") else order
             ref = merge_swarm_results(res["mixed:" + k.split(":")[1]])
-            info = legs[k][0][0].fleet._nominal.launch_info()
-            run[k] = {"launches_per_round": len(legs[k]), "vehicle_steps": int(rk.steps.sum()),
-                      "goal_reached": int((rk.phase == 1).sum()), "replans": int(rk.replans.sum()),
-                      "vehicles_replanned": int((rk.replans > 0).sum()), "launch": info["name"],
-                      "per_wave": info["per_wave"],
+            run[k] = {"launches_per_round": len(legs[k]),
+                      **leg_report(legs[k][0][0], rk, times[k], times["mixed:" + k.split(":")[1]], "over_mixed"),
                       "same_as_mixed": bool(np.array_equal(rk.steps, ref.steps[sel]) and np.array_equal(rk.phase, ref.phase[sel])
                                             and np.array_equal(rk.replan_steps, ref.replan_steps[sel]))}
-            for what, ts in times[k].items():
-                med = float(np.median(ts))
-                run[k][what] = {"median": med, "min": min(ts), "max": max(ts), "all": ts,
-                                "over_mixed": med / float(np.median(times["mixed:" + k.split(":")[1]][what]))}
         out["runs"].append(run)
         for leg in legs.values():
             for sw, _, _ in leg:
-                sw.fleet.close()
+                sw.close()
         print(json.dumps(run), flush=True)
     print(json.dumps(out))
 
@@ -256,76 +231,44 @@ def map_bench(a) -> None:
     [occ, occ with rows 2..33 of columns 36..40 occupied], --epoch-steps, timed the same way on its own.  Per leg:
     medians with min and max of track_replan_s and of the end-to-end run, vehicle-steps, replans (by cause on the
     map legs) and hits; (b) also says whether every vehicle did what it did in (a)."""
-    import torch
-
     from mpcqp import _lib
-    from mpcqp.config import MPCConfig
-    from mpcqp.pipeline.swarm import Swarm
-    from mpcqp.planning.rrt_star import default_planner_parameters
 
-    occ = np.load(ROOT / "rrt-mpc_amd" / "mpcqp" / "data" / "default_plan.npz")["occupancy"]
+    occ = default_grid()
     closed = occ.copy()
     closed[2:34, 36:41] = 0
-    prm = default_planner_parameters()
     out = {"metric": "Swarm.run seconds: the plain fused swarm against the map swarm on an unchanged map, interleaved; "
                      "the closing-passage map alone", "horizon": 15, "sim_steps": a.steps,
            "replan_distance": a.replan_distance, "max_replans": a.max_replans, "lookahead": a.lookahead,
            "epoch_steps": a.epoch_steps, "reps": a.reps, "runs": []}
-    mpc = MPCConfig(horizon=15, sim_steps=a.steps)
 
-    def timed(legs, starts, goals, V):
-        names = list(legs)
-        times = {k: {"track_replan_s": [], "end_to_end_s": []} for k in names}
-        res = {}
-        for r in range(a.reps + 1):  # repeat 0 warms up
-            for k in names[r % len(names):] + names[:r % len(names)]:
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                res[k] = legs[k].run(starts, goals, seeds=np.arange(V))
-                torch.cuda.synchronize()
-                if r:
-                    times[k]["end_to_end_s"].append(time.perf_counter() - t0)
-                    times[k]["track_replan_s"].append(res[k].timings["track_replan_s"])
-        return res, times
-
-    def summary(sw, rk, ts, base=None):
-        info = sw.fleet._nominal.launch_info()
-        d = {"vehicle_steps": int(rk.steps.sum()), "goal_reached": int((rk.phase == 1).sum()),
-             "replans": int(rk.replans.sum()), "replans_with_new_plan": int((rk.replan_steps > 0).sum()),
-             "vehicles_replanned": int((rk.replans > 0).sum()), "launch": info["name"], "per_wave": info["per_wave"]}
+    def leg_summary(sw, rk, ts, base=None):
+        d = {**leg_report(sw, rk, ts, base, "over_plain"), "replans_with_new_plan": int((rk.replan_steps > 0).sum())}
         if rk.replan_cause is not None:
             d["replans_by_cause"] = {name: int((rk.replan_cause == code).sum()) for name, code in
                                      (("aborted", _lib.REPLAN_ABORTED), ("off_track", _lib.REPLAN_OFF_TRACK),
                                       ("blocked", _lib.REPLAN_BLOCKED))}
             d["hits"] = {"vehicle_steps_on_an_occupied_cell": int(rk.hits.sum()), "vehicles": int((rk.hits > 0).sum())}
-        for what, t in ts.items():
-            med = float(np.median(t))
-            d[what] = {"median": med, "min": min(t), "max": max(t), "all": t}
-            if base is not None:
-                d[what]["over_plain"] = med / float(np.median(base[what]))
         return d
 
     for V in a.vehicles:
         starts, goals = pairs(occ, V, 5)
-        kw = dict(map_resolution=0.8, max_vehicles=V, device="cuda:0", replan_distance=a.replan_distance,
-                  max_replans=a.max_replans, fused=True)
-        legs = {"plain": Swarm(occ, mpc, prm, **kw),
-                "map_static": Swarm(occ, mpc, prm, grids=occ[None], lookahead=a.lookahead, **kw)}
-        res, times = timed(legs, starts, goals, V)
+        legs = {"plain": new_swarm(a, V, fused=True),
+                "map_static": new_swarm(a, V, fused=True, grids=occ[None], lookahead=a.lookahead)}
+        res, times = run_swarms(legs, starts, goals, a.reps)
         run = {"vehicles": V, "planned": int(res["plain"].planned.sum()),
-               "plain": summary(legs["plain"], res["plain"], times["plain"]),
-               "map_static": summary(legs["map_static"], res["map_static"], times["map_static"], times["plain"])}
+               "plain": leg_summary(legs["plain"], res["plain"], times["plain"]),
+               "map_static": leg_summary(legs["map_static"], res["map_static"], times["map_static"], times["plain"])}
         p, m = res["plain"], res["map_static"]
         run["map_static"]["same_as_plain"] = bool(
             np.array_equal(p.steps, m.steps) and np.array_equal(p.phase, m.phase)
             and np.array_equal(p.replan_steps, m.replan_steps) and all(np.array_equal(x, y) for x, y in zip(p.states, m.states)))
         for sw in legs.values():
-            sw.fleet.close()
-        closing = {"map_closing": Swarm(occ, mpc, prm, grids=np.stack([occ, closed]), epoch_steps=a.epoch_steps,
-                                        lookahead=a.lookahead, **kw)}
-        res, times = timed(closing, starts, goals, V)
-        run["map_closing"] = summary(closing["map_closing"], res["map_closing"], times["map_closing"])
-        closing["map_closing"].fleet.close()
+            sw.close()
+        closing = {"map_closing": new_swarm(a, V, fused=True, grids=np.stack([occ, closed]), epoch_steps=a.epoch_steps,
+                                            lookahead=a.lookahead)}
+        res, times = run_swarms(closing, starts, goals, a.reps)
+        run["map_closing"] = leg_summary(closing["map_closing"], res["map_closing"], times["map_closing"])
+        closing["map_closing"].close()
         out["runs"].append(run)
         print(json.dumps(run), flush=True)
     print(json.dumps(out))
@@ -358,59 +301,35 @@ def main() -> None:
     ap.add_argument("--epoch-steps", type=int, default=10, help="with --map: steps per grid of the closing-passage map")
     ap.add_argument("--lookahead", type=int, default=20, help="with --map: reference rows the blocked test looks ahead")
     a = ap.parse_args()
-    if a.map:
-        if a.reps < 1:
+    # the first of these that was asked for runs; the interleaved ones take --reps, the warm ones --guess-passes
+    mode = next((fn for on, fn in ((a.map, map_bench), (a.classes, classes_bench), (a.distributed, distributed),
+                                   (a.warm, warm_bench)) if on), None)
+    if mode is not None:
+        if mode is not distributed and a.reps < 1:
             ap.error("--reps must be >= 1")
-        map_bench(a)
-        return
-    if a.classes:
-        if a.reps < 1:
-            ap.error("--reps must be >= 1")
-        if a.guess_passes is None:
+        if mode in (classes_bench, warm_bench) and a.guess_passes is None:
             from mpcqp import _lib
 
             a.guess_passes = [_lib.DEFAULT_GUESS_PASSES]
-        classes_bench(a)
-        return
-    if a.distributed:
-        distributed(a)
-        return
-    if a.warm:
-        if a.reps < 1:
-            ap.error("--reps must be >= 1")
-        if a.guess_passes is None:
-            from mpcqp import _lib
-
-            a.guess_passes = [_lib.DEFAULT_GUESS_PASSES]
-        warm_bench(a)
+        mode(a)
         return
     import torch
 
-    from mpcqp.config import MPCConfig
     from mpcqp.maps.inflate import inflate_binary_occupancy
-    from mpcqp.pipeline.swarm import Swarm
     from mpcqp.planning.rrt_star import BatchedRRTStarPlanner, default_planner_parameters, draw_samples
 
-    d = np.load(ROOT / "rrt-mpc_amd" / "mpcqp" / "data" / "default_plan.npz")
-    occ = d["occupancy"]
+    occ = default_grid()
     out = {"grid": list(occ.shape), "runs": []}
     prm = default_planner_parameters()
     for V in a.vehicles:
         starts, goals = pairs(occ, V, 5)
-        sw = Swarm(occ, MPCConfig(horizon=15, sim_steps=a.steps), prm, map_resolution=0.8, max_vehicles=V,
-                   device="cuda:0", replan_distance=a.replan_distance, max_replans=a.max_replans, fused=a.fused)
+        sw = new_swarm(a, V, fused=a.fused)
         sw.run(starts[:4], goals[:4], seeds=np.arange(4), sim_steps=5)  # warm
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        res = sw.run(starts, goals, seeds=np.arange(V), check_every=50)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        ok_replans = int((res.replan_steps > 0).sum())
+        dt, res = timed(lambda: sw.run(starts, goals, seeds=np.arange(V), check_every=50), torch.cuda.synchronize,
+                        time.perf_counter)
         run = {"vehicles": V, "mode": "fused loop (mpcqp_swarm_loop)" if a.fused else "graph-stepped (mpcqp_swarm_run)",
-               "seconds": dt, "vehicle_steps": int(res.steps.sum()),
-               "vehicle_steps_per_s": int(res.steps.sum()) / dt,
-               "planned": int(res.planned.sum()), "goal_reached": int((res.phase == 1).sum()),
-               "replans": int(res.replans.sum()), "replans_with_new_plan": ok_replans,
+               "seconds": dt, **loop_counts(res, SWARM_COUNTS), "vehicle_steps_per_s": int(res.steps.sum()) / dt,
+               "planned": int(res.planned.sum()), "replans_with_new_plan": int((res.replan_steps > 0).sum()),
                "vehicles_replanned": int((res.replans > 0).sum()),
                "trigger": f"per step on the device: off track > {a.replan_distance} px or aborted, "
                           f"<= {a.max_replans} replans per vehicle",
