@@ -266,6 +266,51 @@ template <int L>
 __device__ __forceinline__ void fmac_bc(double& acc, double w, double m) {
   asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(w), "v"(m), "i"(L));
 }
+// ---- the sweep's pivot step (Ctx::sweep, Ctx::sweep_reg)
+// One step's coefficient and new r[k] from rk = r[k] and inv = 1/d, five VALU instructions:
+//   every lane:        coef = -(rk * inv)  (the product with inv's source negation: a product's sign
+//                      is the xor of its operands' signs, so these are the negated product's bits,
+//                      zeros and infinities included)  and  rk = rk * inv;
+//   the pivot lanes:   coef = inv - 1.0  and  rk = -inv  (inv * -1.0: exact, no rounding, and inv, an
+//                      FMA's result, is already in the kernel's denormal mode), written under an exec
+//                      mask of those lanes alone.
+// K2 == K, a QP on the whole wave: lane K, and all 64 lanes active afterwards -- as they are before: the
+// whole-wave sweep's permlane and DPP broadcasts read every lane.  Otherwise the pair layout: lanes K and
+// K2, cut to the active lanes (the other half may be masked off) and the exec mask restored.  The mask is
+// built from inline constants inside the statement (in exec itself, or in vcc): as an SGPR operand the
+// compiler keeps the sweep's 2N masks live through the kernel and spills SGPRs, and the fused loops
+// have none to spare.  One asm statement, so the compiler
+// neither pads between its instructions nor rewrites -(rk * inv) into integer operations on rk * inv.
+template <int K, int K2>
+__device__ __forceinline__ void pivot_step(double& coef, double& rk, double inv) {
+  if constexpr (K2 == K) {  // the whole wave is active: its sweep's broadcasts need that already
+    asm volatile(
+        "v_mul_f64 %[c], %[r], -%[i]\n\t"
+        "v_mul_f64 %[r], %[r], %[i]\n\t"
+        "s_lshl_b64 exec, 1, %[k]\n\t"
+        "v_add_f64 %[c], %[i], -1.0\n\t"
+        "v_mul_f64 %[r], %[i], -1.0\n\t"
+        "s_mov_b64 exec, -1"
+        : [c] "=&v"(coef), [r] "+v"(rk)
+        : [i] "v"(inv), [k] "n"(K)
+        : "scc");
+  } else {
+    uint64_t saved;
+    asm volatile(
+        "s_lshl_b64 vcc, 1, %[k]\n\t"
+        "v_mul_f64 %[c], %[r], -%[i]\n\t"
+        "s_bitset1_b64 vcc, %[k2]\n\t"
+        "v_mul_f64 %[r], %[r], %[i]\n\t"
+        "s_and_saveexec_b64 %[sv], vcc\n\t"
+        "v_add_f64 %[c], %[i], -1.0\n\t"
+        "v_mul_f64 %[r], %[i], -1.0\n\t"
+        "s_mov_b64 exec, %[sv]"
+        : [c] "=&v"(coef), [r] "+v"(rk), [sv] "=&s"(saved)
+        : [i] "v"(inv), [k] "n"(K), [k2] "n"(K2)
+        : "scc", "vcc");
+  }
+}
+
 // ---- lane policies of the one-wave solver: a QP owns the whole wave (Lanes<false>, the layout
 // above) or one 32-lane half of it (Lanes<true>: two QPs per wave, lanes 0-31 and 32-63, for
 // n = 2N <= 30, where a whole-wave QP leaves lanes 30..63 computing on padding).  Every cross-lane

@@ -317,7 +317,21 @@ struct Ctx {
   // row_newbcast, so each update r[j] += coef * A[k][j] is one v_fmac_f64_dpp.  The pivot row itself
   // is the same FMA with coef = 1/d - 1 (A[k][j] <- A[k][j] / d), so the update is uniform over
   // lanes.  The step loop is unrolled at compile time (static register indices and DPP lane
-  // immediates).  false on a non-positive pivot.
+  // immediates).  false on a pivot that is not positive and finite.
+  // The pivot lane's fix-ups: with inv = 1/d, every lane computes ck = r[k] * inv (the new r[k], in
+  // r[k]'s place) and the FMAs' coefficient -ck (a second product with the source negation: the same
+  // bits as negating ck).  The unrolled loop knows the pivot lane statically, so its two values,
+  // coef = inv - 1 and r[k] = -inv, are written before the FMAs by two instructions under a one-lane
+  // exec mask (pivot_step; the pair layout: lanes k and 32 + k, each from its half's inv): no
+  // lane-id compare and no selects, and inv is dead once the FMAs start.
+  // The pivot test is decided once, after the last step, from the running minimum of the pivots (one
+  // v_min_f64 per step, which drops a NaN) and the last pivot: ok = min_k d_k > 0 && isfinite(d_last).
+  // That is false exactly when some d_k is not positive and finite.  A d_k <= 0 (-inf, -0 and +0
+  // included) brings the minimum to <= 0, where it stays.  A d_k that is NaN or +inf gives inv = NaN
+  // (rcp(+inf) = +0 and fma(-inf, +0, 1) = NaN), so coef is NaN on every lane (inv - 1 and
+  // -(r[k] * inv)), every r[j], j != k, of every lane becomes NaN, and so does each later pivot:
+  // d_last is NaN, or d_k is d_last itself.  With every d_k positive and finite both tests pass.
+  // Lanes of a half see only their half's pivots, so the pair layout decides per half.
   // The column goes through LDS (one ds_write as soon as the previous step has updated it, kNW reads
   // of the row's values and one uniform read of the pivot; double buffered, the QP's own buffer -- a
   // half's in the pair layout) rather than permlane swaps and readlanes: fourteen VALU instructions
@@ -329,9 +343,14 @@ struct Ctx {
   // against ~3.6k cycles per N = 10 factorization (profiles/r05_n_stamps/, r05_o_ab_register_sweep_n_le_32.json).  Those sizes
   // and the pair layout keep the register broadcasts (sweep_reg).
   static constexpr bool kRegBcast = Pair || kNW <= 2;
+  // the lanes that hold pivot k: lane k, and lane 32 + k for the upper half's QP in the pair layout
+  template <int K>
+  __device__ __forceinline__ static void pivot_fix(double& coef, double& rk, double inv) {
+    pivot_step<K, Pair ? 32 + K : K>(coef, rk, inv);
+  }
   __device__ __forceinline__ bool sweep() {
     if constexpr (kRegBcast) return sweep_reg();
-    bool ok = true;
+    double dmin = 0.0, dlast = 0.0;
     int ln = lane;
     asm volatile("" : "+v"(ln));
     const int rl = ln & 15;
@@ -351,13 +370,14 @@ struct Ctx {
       const double d = bk[k];
       // DPP reads of a VGPR need two wait states after its write; tie the pad to w
       asm volatile("s_nop 1" : "+v"(w[0]));
-      ok = ok && (d > 0.0) && isfinite(d);
+      if constexpr (k == 0) dmin = d;
+      else dmin = min_nc(dmin, d);
+      if constexpr (k == n - 1) dlast = d;
       double inv = __builtin_amdgcn_rcp(d);
       inv = fma(inv, fma(-d, inv, 1.0), inv);
       inv = fma(inv, fma(-d, inv, 1.0), inv);
-      const bool piv = lane == k;
-      const double ck = r[k] * inv;
-      const double coef = piv ? inv - 1.0 : -ck;
+      double coef, ck = r[k];
+      pivot_fix<k>(coef, ck, inv);
       // the next pivot column first, published for the next step
       if constexpr (k + 1 < n) {
         fmac_bc<(k + 1) % 16>(r[k + 1], w[(k + 1) / 16], coef);
@@ -367,17 +387,23 @@ struct Ctx {
         constexpr int j = decltype(jc)::value;
         if constexpr (j != k && j != k + 1) fmac_bc<j % 16>(r[j], w[j / 16], coef);
       });
-      r[k] = piv ? -inv : ck;
+      r[k] = ck;
     });
     lds_sync();
-    return ok;
+    return (dmin > 0.0) && isfinite(dlast);
   }
   // The register-broadcast sweep (n <= 32 and the pair layout): the column by vbcast, the pivot by
   // readlane (whole wave; 1/d is computed while the broadcast is in flight) or from the half's DPP
   // row (pair layout).  Staging through LDS measured 8 % slower in the pair layout (43.8M -> 40.2M
   // QP/s at N = 15, B = 16384, profiles/r05_i_ab.json).
+  // The pivot test: the pair layout's as sweep()'s.  On the whole wave the pivot is in SGPRs, and the
+  // test costs no vector instruction and no register: d is positive and finite exactly when its high
+  // word, unsigned, is below 0x7ff00000 (sign clear, exponent not all ones) and its words are not both
+  // zero, so the running maximum of the high words and the running minimum of hi | lo (scalar
+  // instructions) decide after the last step.
   __device__ __forceinline__ bool sweep_reg() {
-    bool ok = true;
+    double dmin = 0.0, dlast = 0.0;
+    uint32_t hi_max = 0u, any_min = ~0u;
     Unroll<0, n>::run([&](auto kc) {
       constexpr int k = decltype(kc)::value;
       double d, w[4];
@@ -388,22 +414,31 @@ struct Ctx {
         d = readlane(r[k], k);
         vbcast(r[k], w);
       }
-      ok = ok && (d > 0.0) && isfinite(d);
+      if constexpr (Pair) {
+        if constexpr (k == 0) dmin = d;
+        else dmin = min_nc(dmin, d);
+        if constexpr (k == n - 1) dlast = d;
+      } else {
+        const uint32_t hi = (uint32_t)__double2hiint(d), lo = (uint32_t)__double2loint(d);
+        hi_max = hi > hi_max ? hi : hi_max;
+        const uint32_t any = hi | lo;
+        any_min = any < any_min ? any : any_min;
+      }
       double inv = __builtin_amdgcn_rcp(d);
       inv = fma(inv, fma(-d, inv, 1.0), inv);
       inv = fma(inv, fma(-d, inv, 1.0), inv);
-      const bool piv = lane == k;
-      const double ck = r[k] * inv;
-      const double coef = piv ? inv - 1.0 : -ck;
+      double coef, ck = r[k];
+      pivot_fix<k>(coef, ck, inv);
       // next pivot column first: the next step's broadcast depends only on it
       if constexpr (k + 1 < n) fmac_bc<(k + 1) % 16>(r[k + 1], w[(k + 1) / 16], coef);
       Unroll<0, n>::run([&](auto jc) {
         constexpr int j = decltype(jc)::value;
         if constexpr (j != k && j != k + 1) fmac_bc<j % 16>(r[j], w[j / 16], coef);
       });
-      r[k] = piv ? -inv : ck;
+      r[k] = ck;
     });
-    return ok;
+    if constexpr (Pair) return (dmin > 0.0) && isfinite(dlast);
+    else return hi_max < 0x7ff00000u && any_min != 0u;
   }
   // Rank-1 change of the factorized matrix, A' = A + delta c c' with c the row (tau, l) of
   // Cbar (Sherman-Morrison): A'^{-1} = A^{-1} - kappa u u', u = A^{-1} c,

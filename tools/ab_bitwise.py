@@ -41,8 +41,18 @@ MID_CASES = [  # the mid-horizon kernel (N = 33..64)
     ("config3", 53, 256, "auto", {}),
     ("config3", 61, 256, "auto", {}),
 ]
+EXTRA_CASES = [  # the sweep's other paths: the first LDS-column horizon, packed Pbar, no padding lane, a small pair
+    ("config3", 17, 1024, "auto", {}),
+    ("config3", 24, 1024, "auto", {}),
+    ("config3", 32, 1024, "auto", {}),
+    ("config3", 9, 4096, "on", {}),
+    ("config3", 16, 1024, "off", {}),
+    ("config3", 15, 4096, "on", {"max_iter": 40, "polish": 0}),
+]
 if os.environ.get("MPCQP_AB_MID") == "1":
     CASES = MID_CASES
+if os.environ.get("MPCQP_AB_EXTRA") == "1":
+    CASES = CASES + EXTRA_CASES
 # --loops: (kind, ...) with pairing last.  "fleet": horizon, steps (None: to the end) -- V = 5 on plans of
 # different lengths (test_gpu_warm_pair.py); "carry": horizon, the launches before the rest -- V = 4 on the
 # golden plan; "swarm": V, steps, replan distance, max_replans, seed (test_gpu_swarm_warm.py's swarms)
@@ -129,9 +139,14 @@ def main() -> None:
     ap.add_argument("--child", default=None)
     ap.add_argument("--mid", action="store_true", help="the mid-horizon cases (N = 33..64) instead")
     ap.add_argument("--loops", action="store_true", help="also the warm fused loops (fleet, carried, swarm)")
+    ap.add_argument("--extra", action="store_true", help="also EXTRA_CASES (N = 17, 24, 32, 16, pairs at 9 and 15)")
     a = ap.parse_args()
     if a.mid:
         os.environ["MPCQP_AB_MID"] = "1"
+    if a.extra:  # the children read the environment; this process lists the cases in its summary
+        global CASES
+        os.environ["MPCQP_AB_EXTRA"] = "1"
+        CASES = CASES + EXTRA_CASES
     if a.child:
         child(a.child, a.loops)
         return

@@ -13,10 +13,10 @@
 #endif
 constexpr int NN = SB_N, nn = 2 * SB_N, REPS = 16;
 
-// the sweep with the pivot column broadcast staged through LDS (one ds_write, kNW ds_reads per step)
-// instead of the permlane swaps: the variant under test
+// The sweep with the previous pivot step, for comparison with Ctx::sweep's (same LDS broadcast, same
+// FMAs): the pivot lane's two values by selects on a lane-id compare, the pivot test in every step.
 template <class Cx>
-__device__ __forceinline__ bool sweep_lds(Cx& C, double* __restrict__ buf) {
+__device__ __forceinline__ bool sweep_select(Cx& C, double* __restrict__ buf) {
   constexpr int n = Cx::n, NW = Cx::kNW;
   bool ok = true;
   const int lane = C.lane;
@@ -84,6 +84,7 @@ __global__ __launch_bounds__(64, 2) void k_bench(const double* __restrict__ A, d
   Ctx<NN> C;
   const int lane = threadIdx.x;
   C.init(lane, 0.1, sm.solve);
+  C.colb = sm.col;
 #pragma unroll
   for (int j = 0; j < nn; ++j) C.r[j] = lane < nn ? A[j * 64 + lane] : 0.0;
   double v = lane < nn ? 1.0 + 0.001 * lane : 0.0;
@@ -93,7 +94,7 @@ __global__ __launch_bounds__(64, 2) void k_bench(const double* __restrict__ A, d
     if constexpr (MODE == 0) {
       ok = C.sweep() && ok;
     } else if constexpr (MODE == 2) {
-      ok = sweep_lds(C, bbuf) && ok;
+      ok = sweep_select(C, bbuf) && ok;
     } else if constexpr (MODE == 3) {
       v = inv_mul_lds(C, v, bbuf) * 0.5;
     } else {
@@ -148,7 +149,7 @@ int main() {
   hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0);
   for (int per : {1, 2}) {
     run<0>("sweep", cus * 4 * per, dA);
-    run<2>("sweep_lds_bcast", cus * 4 * per, dA);
+    run<2>("sweep_select_step", cus * 4 * per, dA);
     run<1>("inv_mul", cus * 4 * per, dA);
     run<3>("inv_mul_lds_bcast", cus * 4 * per, dA);
   }
